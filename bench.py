@@ -12,6 +12,12 @@ Models (BASELINE.json configs):
 
 bf16 compute + fp32 master Adam/AdamW, synthetic data (no-network env),
 weak scaling (per-GPU batch fixed), RCCL DDP via deepdfa_amd.parallel.
+
+A plain run only sets up, warms up, times --steps steps and prints one JSON
+line. --dump-outputs DIR also writes loss, gradients and updated parameters
+of the timed path, run on the last timed step's batch from the seeded start
+state, as .npy; --full is where any secondary measurement belongs
+(docs/BENCH.md).
 """
 
 import argparse
@@ -253,6 +259,64 @@ def build_codet5(args, rank, device, use_cuda, with_ddfa: bool):
     return model, opt_fn, make_step, meta, False
 
 
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # per array: 16 MB fp32, 3 arrays < 64 MB
+
+
+def snapshot_state(model, opt):
+    """Clone the seeded start state: master params, Adam moments, buffers."""
+    return {
+        "flat_p": opt.flat_p.detach().clone(),
+        "m": opt.m.detach().clone(),
+        "v": opt.v.detach().clone(),
+        "buffers": [b.detach().clone() for b in model.buffers()],
+    }
+
+
+@torch.no_grad()
+def rewind_state(model, opt, state):
+    """Put the start state back IN PLACE: the captured graphs hold the
+    addresses of these tensors (device step counter included), so nothing
+    may be re-allocated."""
+    opt.flat_p.copy_(state["flat_p"])
+    opt.m.copy_(state["m"])
+    opt.v.copy_(state["v"])
+    opt.flat_g.zero_()
+    if opt.flat_p16 is not None:
+        opt.flat_p16.copy_(opt.flat_p)
+    opt.step_count = 0
+    if hasattr(opt, "_step_t"):
+        opt._step_t.zero_()
+    for b, b0 in zip(model.buffers(), state["buffers"]):
+        b.copy_(b0)
+    if opt.flat_p.is_cuda:
+        from deepdfa_amd.ops.transformer import bump_weights_epoch
+
+        bump_weights_epoch()  # eager path: drop the cached bf16 weight casts
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write what the dump step produced — its loss, the gradients it left
+    and the parameters after its optimizer update — as float32 .npy.
+    Arrays over DUMP_MAX_ELEMS are reduced to a fixed seeded sample."""
+    import numpy as np
+
+    def flat(ts):
+        return torch.cat([t.detach().float().flatten() for t in ts]).cpu()
+
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu(),
+        "params": flat(model.parameters()),
+        "grads": flat(p.grad for p in model.parameters() if p.grad is not None),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.numel() > DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, a.numel(), (DUMP_MAX_ELEMS,), generator=gen)
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,6 +326,13 @@ def main():
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--n-batches", type=int, default=4)
     ap.add_argument("--no-graph-capture", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rewind to the seeded start state, "
+                         "run the timed path on the last step's batch and write its "
+                         "loss, gradients and updated parameters as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; the benchmark "
+                         "has none beyond the headline figure, so this adds nothing yet")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = {"ddfa": 256, "linevul": 16, "linevul_ddfa": 16, "codet5": 8, "codet5_ddfa": 8}[args.model]
@@ -313,6 +384,7 @@ def main():
             with torch.no_grad():
                 torch.distributed.broadcast(opt.flat_p, src=0)
     step = make_step(opt, ddp, set_to_none=not use_graphs)
+    start_state = snapshot_state(model, opt) if args.dump_outputs else None
 
     for i in range(args.warmup):
         step(i)
@@ -324,6 +396,7 @@ def main():
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         graphs = []
+        losses = []  # static loss tensor of each captured step
         # multi-rank: capture the compute only (fwd+bwd); the RCCL
         # all-reduce + optimizer run eagerly between replays so no
         # collective sits inside a hipGraph (and N>1 keeps the captured
@@ -334,7 +407,7 @@ def main():
             for i in range(args.n_batches):
                 cg = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(cg, pool=pool):
-                    capture_fn(i)
+                    losses.append(capture_fn(i))
                 graphs.append(cg)
             torch.cuda.synchronize()
 
@@ -342,6 +415,7 @@ def main():
                 graphs[i % len(graphs)].replay()
                 if finish_fn is not None:
                     finish_fn()
+                return losses[i % len(graphs)]
         except RuntimeError as e:  # capture unsupported: stay eager
             print(f"[bench] graph capture failed ({e}); running eager",
                   file=sys.stderr)
@@ -359,6 +433,19 @@ def main():
         step(i)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and args.steps > 0:
+        # The float atomics of the weight-gradient kernels make summation
+        # order vary, and W+K training steps amplify that until two runs no
+        # longer agree. So the dump is the timed path (same replayed graph
+        # or step function, same batch as the last timed step) run once
+        # more from the seeded start state: identical inputs every run,
+        # outputs equal up to fp32 summation order.
+        rewind_state(model, opt, start_state)
+        dump_loss = step(args.steps - 1)
+        barrier_sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dump_loss, model)
 
     print(f"[bench] rank {rank}: elapsed {elapsed:.4f}s over {args.steps} steps",
           file=sys.stderr)

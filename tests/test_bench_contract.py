@@ -29,6 +29,41 @@ def test_bench_single_process_cpu():
     _check_json(out.stdout.strip().splitlines()[-1], 1)
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the dump step's arrays as float32 .npy. The dump
+    step is the timed path run on the last timed step's batch from the seeded
+    start state, so it does not depend on how many steps trained before it:
+    3 timed + 1 warmup steps and 1 timed step (both end on batch 0 of 2) must
+    dump the same arrays (the CPU path has no atomics: bit for bit). --full
+    is accepted and leaves the result line unchanged in meaning."""
+    import numpy as np
+
+    dumps = []
+    for name, steps, warmup, extra in (("a", 3, 1, []), ("b", 1, 0, ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps),
+             "--warmup", str(warmup), "--batch", "8", "--n-batches", "2",
+             "--dump-outputs", str(d)] + extra,
+            cwd=REPO, capture_output=True, text=True, timeout=300,
+        )
+        assert out.returncode == 0, out.stderr[-2000:]
+        row = _check_json(out.stdout.strip().splitlines()[-1], 1)
+        assert row["steps"] == steps and row["warmup"] == warmup
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["grads.npy", "loss.npy", "params.npy"]
+        arrs = {f: np.load(d / f) for f in files}
+        for f, a in arrs.items():
+            assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 1024 * 1024
+        assert arrs["loss.npy"].shape == (1,)
+        assert arrs["params.npy"].shape == arrs["grads.npy"].shape
+        assert np.abs(arrs["grads.npy"]).max() > 0
+        dumps.append(arrs)
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f])
+
+
 def test_bench_torchrun_two_ranks_gloo():
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
