@@ -1107,6 +1107,110 @@ std::vector<at::Tensor> mlp3_bwd(at::Tensor dlogits, at::Tensor x, at::Tensor h1
   return {dx, dW1, dW2, dW3, db1, db2, db3};
 }
 
+// ---------------------------------------------------------------------------
+// Fused node-level head (csrc/node_head.hip): D1 = D2 = 128, D = 256 only.
+// ---------------------------------------------------------------------------
+void launch_node_head_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                          const __hip_bfloat16*, const float*, const float*, const float*,
+                          const float*, float*, __hip_bfloat16*, __hip_bfloat16*,
+                          __hip_bfloat16*, int, int, int, hipStream_t);
+void launch_node_head_bwd(const float*, const __hip_bfloat16*, const __hip_bfloat16*,
+                          const __hip_bfloat16*, const __hip_bfloat16*, const float*,
+                          __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*,
+                          float*, float*, int, int, hipStream_t);
+int node_head_tile_rows(int, int);
+
+static void check_node_head_w(const at::Tensor& W, const char* name) {
+  TORCH_CHECK(W.is_cuda() && W.is_contiguous() && W.scalar_type() == at::kBFloat16 &&
+              W.dim() == 2 && W.size(0) == 256 && W.size(1) == 256,
+              name, " must be a contiguous (256,256) bf16 GPU tensor");
+}
+static void check_node_head_v(const at::Tensor& v, long n, const char* name) {
+  TORCH_CHECK(v.is_cuda() && v.is_contiguous() && v.scalar_type() == at::kFloat &&
+              v.numel() == n, name, " must be a contiguous fp32 GPU tensor of ", n,
+              " elements");
+}
+
+// returns {logits} or, with save, {logits, X = [h|fe], H1, H2}
+std::vector<at::Tensor> node_head_fwd(at::Tensor h, at::Tensor fe, at::Tensor W1,
+                                      at::Tensor W2, at::Tensor b1, at::Tensor b2,
+                                      at::Tensor w3, at::Tensor b3, bool save,
+                                      int64_t tile_rows) {
+  CHECK_GPU(h);
+  CHECK_GPU(fe);
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && fe.scalar_type() == at::kBFloat16,
+              "node_head_fwd: h and fe must be bf16");
+  TORCH_CHECK(h.dim() == 2 && fe.dim() == 2 && h.size(1) == 128 && fe.size(1) == 128 &&
+              h.size(0) == fe.size(0),
+              "node_head_fwd supports only D1 = D2 = 128 (D = 256)");
+  check_node_head_w(W1, "W1");
+  check_node_head_w(W2, "W2");
+  check_node_head_v(b1, 256, "b1");
+  check_node_head_v(b2, 256, "b2");
+  check_node_head_v(w3, 256, "w3");
+  check_node_head_v(b3, 1, "b3");
+  const int N = h.size(0);
+  auto logits = at::empty({N}, h.options().dtype(at::kFloat));
+  at::Tensor X, H1, H2;
+  if (save) {
+    X = at::empty({N, 256}, h.options());
+    H1 = at::empty({N, 256}, h.options());
+    H2 = at::empty({N, 256}, h.options());
+  }
+  launch_node_head_fwd(ptr<bf16_t>(h), ptr<bf16_t>(fe), ptr<bf16_t>(W1), ptr<bf16_t>(W2),
+                       b1.data_ptr<float>(), b2.data_ptr<float>(), w3.data_ptr<float>(),
+                       b3.data_ptr<float>(), logits.data_ptr<float>(),
+                       save ? mptr<bf16_t>(X) : nullptr, save ? mptr<bf16_t>(H1) : nullptr,
+                       save ? mptr<bf16_t>(H2) : nullptr, N, save ? 1 : 0, (int)tile_rows,
+                       cur_stream());
+  if (save) return {logits, X, H1, H2};
+  return {logits};
+}
+
+// returns {dh, dfe, dH1, dH2, dW3, db3}; dW3/db3 ACCUMULATE into out_w3 /
+// out_b3 (live fp32 .grad views) when given, else into fresh zeros
+std::vector<at::Tensor> node_head_bwd(at::Tensor dlogits, at::Tensor H1, at::Tensor H2,
+                                      at::Tensor W1T, at::Tensor W2T, at::Tensor w3,
+                                      c10::optional<at::Tensor> out_w3,
+                                      c10::optional<at::Tensor> out_b3,
+                                      int64_t tile_rows) {
+  CHECK_GPU(dlogits);
+  CHECK_GPU(H1);
+  CHECK_GPU(H2);
+  const int N = H1.size(0);
+  TORCH_CHECK(H1.scalar_type() == at::kBFloat16 && H2.scalar_type() == at::kBFloat16 &&
+              H1.dim() == 2 && H1.size(1) == 256 && H2.dim() == 2 && H2.size(1) == 256 &&
+              H2.size(0) == N, "node_head_bwd: H1, H2 must be (N,256) bf16");
+  check_node_head_v(dlogits, N, "dlogits");
+  check_node_head_w(W1T, "W1T");
+  check_node_head_w(W2T, "W2T");
+  check_node_head_v(w3, 256, "w3");
+  auto fopt = H1.options().dtype(at::kFloat);
+  at::Tensor dW3, db3;
+  if (out_w3.has_value()) {
+    dW3 = *out_w3;
+    check_node_head_v(dW3, 256, "out_w3");
+  } else {
+    dW3 = at::zeros({1, 256}, fopt);
+  }
+  if (out_b3.has_value()) {
+    db3 = *out_b3;
+    check_node_head_v(db3, 1, "out_b3");
+  } else {
+    db3 = at::zeros({1}, fopt);
+  }
+  auto dH1 = at::empty_like(H1);
+  auto dH2 = at::empty_like(H2);
+  auto dh = at::empty({N, 128}, H1.options());
+  auto dfe = at::empty({N, 128}, H1.options());
+  launch_node_head_bwd(dlogits.data_ptr<float>(), ptr<bf16_t>(H1), ptr<bf16_t>(H2),
+                       ptr<bf16_t>(W2T), ptr<bf16_t>(W1T), w3.data_ptr<float>(),
+                       mptr<bf16_t>(dH1), mptr<bf16_t>(dH2), mptr<bf16_t>(dh),
+                       mptr<bf16_t>(dfe), dW3.data_ptr<float>(), db3.data_ptr<float>(), N,
+                       (int)tile_rows, cur_stream());
+  return {dh, dfe, dH1, dH2, dW3, db3};
+}
+
 void adamw_fused(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr,
                  double beta1, double beta2, double eps, double weight_decay, at::Tensor step,
                  c10::optional<at::Tensor> gclip, bool l2_mode,
@@ -1363,6 +1467,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("l2_mode") = false,
         pybind11::arg("p16") = pybind11::none());
   m.def("softmax_mask_bwd", &softmax_mask_bwd);
+  m.def("node_head_fwd", &node_head_fwd, pybind11::arg("h"), pybind11::arg("fe"),
+        pybind11::arg("W1"), pybind11::arg("W2"), pybind11::arg("b1"), pybind11::arg("b2"),
+        pybind11::arg("w3"), pybind11::arg("b3"), pybind11::arg("save") = true,
+        pybind11::arg("tile_rows") = 0);
+  m.def("node_head_bwd", &node_head_bwd, pybind11::arg("dlogits"), pybind11::arg("H1"),
+        pybind11::arg("H2"), pybind11::arg("W1T"), pybind11::arg("W2T"), pybind11::arg("w3"),
+        pybind11::arg("out_w3") = pybind11::none(), pybind11::arg("out_b3") = pybind11::none(),
+        pybind11::arg("tile_rows") = 0);
+  m.def("node_head_tile_rows", [](int64_t N, int64_t tile) {
+    return node_head_tile_rows((int)N, (int)tile);
+  }, pybind11::arg("N"), pybind11::arg("tile_rows") = 0);
   m.def("ggnn_fused_bwd", &ggnn_fused_bwd, pybind11::arg("grad_out"),
         pybind11::arg("t_indptr"), pybind11::arg("t_indices"), pybind11::arg("x"),
         pybind11::arg("W_eT"), pybind11::arg("WcatT"), pybind11::arg("HH"),

@@ -65,8 +65,64 @@ class BaseModule(nn.Module):
         elif self.label_style == "graph":
             label = segment_max(graph.ndata["_VULN"].float(), graph)
         else:
-            raise NotImplementedError(self.label_style)
+            # dataflow_solution_in/out: the reference's own dataset never
+            # attaches _DF_IN/_DF_OUT, so there is nothing to train on
+            raise NotImplementedError(
+                f"label_style={self.label_style!r} is not supported: only "
+                "'graph' and 'node' are; the dataflow_solution_in/out styles "
+                "need per-node _DF_IN/_DF_OUT labels that no dataset here (nor "
+                "the reference's) attaches"
+            )
         return label.float()
+
+    # -- node-level masks -----------------------------------------------------
+
+    @staticmethod
+    def node_weight(graph, graph_weight: torch.Tensor) -> torch.Tensor:
+        """Expand a per-graph weight (b,) to per-node (N,): node i takes the
+        weight of the graph whose [offset, next offset) range holds it.
+        Static-shape ops on graph.node_offsets only — recomputed every step,
+        so a capture bucket whose static node_offsets are refilled before a
+        replay gets the new batch's segments (BatchedCFG.segment_ids()
+        caches its result and would go stale there)."""
+        offs = graph.node_offsets
+        n = graph.ndata["_VULN"].shape[0]
+        idx = torch.arange(n, device=offs.device, dtype=offs.dtype)
+        seg = torch.bucketize(idx, offs[1:], right=True)
+        seg = seg.clamp_(max=graph_weight.shape[0] - 1)
+        return graph_weight[seg]
+
+    def undersample_node_mask(
+        self, label: torch.Tensor, valid: Optional[torch.Tensor] = None
+    ) -> Optional[torch.Tensor]:
+        """0/1 node mask for undersample_node_on_loss_factor (reference
+        base_module.py:171-199): every positive node plus
+        k = min(round(n_pos * factor), n_neg) negatives drawn uniformly
+        without replacement. None when the factor is unset. `valid` (0/1
+        per node) keeps padding nodes out of the negative pool. The reference
+        raises when k > n_neg; here k is clamped (docs/PARITY.md). The
+        generator is module-owned and seeded from torch.initial_seed() at
+        first use, so seed_everything makes the draws reproducible."""
+        factor = self.hparams.get("undersample_node_on_loss_factor")
+        if factor is None:
+            return None
+        gen = getattr(self, "_node_sample_gen", None)
+        if gen is None:
+            gen = torch.Generator()  # CPU: the draw is index bookkeeping
+            gen.manual_seed(torch.initial_seed())
+            self._node_sample_gen = gen
+        lab = label.detach().to("cpu")
+        pos = (lab > 0).nonzero(as_tuple=True)[0]
+        is_neg = lab <= 0
+        if valid is not None:
+            is_neg &= valid.detach().to("cpu") > 0
+        neg = is_neg.nonzero(as_tuple=True)[0]
+        k = min(int(round(pos.numel() * float(factor))), neg.numel())
+        keep = neg[torch.randperm(neg.numel(), generator=gen)[:k]]
+        mask = torch.zeros(lab.shape[0], dtype=torch.float32)
+        mask[pos] = 1.0
+        mask[keep] = 1.0
+        return mask.to(label.device)
 
     # -- loss -----------------------------------------------------------------
 
@@ -91,9 +147,12 @@ class BaseModule(nn.Module):
         graph, extrafeats = batch if isinstance(batch, tuple) else (batch, {})
         label = self.get_label(graph)
         logits = self(graph, extrafeats)
-        loss = self.loss_fn(logits.float(), label)
+        mask = self.undersample_node_mask(label) if self.label_style == "node" else None
+        loss = self.loss_fn(logits.float(), label, weight=mask)
         with torch.no_grad():
-            self.metrics["train"].to(logits.device).update(torch.sigmoid(logits.float()), label)
+            self.metrics["train"].to(logits.device).update(
+                torch.sigmoid(logits.float()), label, mask=mask
+            )
         return loss
 
     def training_step_masked(self, graph, extrafeats, weight: torch.Tensor) -> torch.Tensor:
@@ -102,6 +161,12 @@ class BaseModule(nn.Module):
         graphs contribute zero loss, zero gradient and zero metric counts."""
         label = self.get_label(graph)
         logits = self(graph, extrafeats)
+        if self.label_style == "node":
+            # per-graph 0/1 -> per-node 0/1 (dummy-graph nodes get 0)
+            weight = self.node_weight(graph, weight)
+            mask = self.undersample_node_mask(label, valid=weight)
+            if mask is not None:  # eager only: data-dependent k, never captured
+                weight = mask
         loss = self.loss_fn(logits.float(), label, weight=weight)
         with torch.no_grad():
             self.metrics["train"].to(logits.device).update(

@@ -229,6 +229,24 @@ class FlowGNNGGNNModule(BaseModule):
                 return mlp3(out, self.output_layer[0], self.output_layer[2],
                             self.output_layer[4])
             return self.output_layer(out).squeeze(-1)
+        # node-level head (GPU bf16): split-A concat + the 3-layer MLP over
+        # every node as one MFMA kernel each way (csrc/node_head.hip); the
+        # eager tail was three library GEMMs + ReLU/bias glue over an
+        # (N,256) concatenation
+        if (
+            self.label_style == "node"
+            and not self.encoder_mode
+            and ggnn_out.is_cuda
+            and ggnn_out.dtype == torch.bfloat16
+            and self.out_dim == 256
+            and ggnn_out.shape[1] == 128
+            and len(self.output_layer) == 5
+        ):
+            from ..ops import flowgnn as _fops
+
+            return _fops.node_head(ggnn_out, feat_embed.to(ggnn_out.dtype),
+                                   self.output_layer[0], self.output_layer[2],
+                                   self.output_layer[4])
         out = torch.cat([ggnn_out, feat_embed.to(ggnn_out.dtype)], dim=-1)
         if self.label_style == "graph":
             out = self.pooling(graph, out)

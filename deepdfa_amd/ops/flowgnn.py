@@ -452,6 +452,125 @@ def mlp3(x, lin1, lin2, lin3):
                        lin3.weight, lin3.bias, w1t, w2t)
 
 
+def _node_head_cache(lin1: torch.nn.Linear, lin2: torch.nn.Linear):
+    """bf16 operands of the fused node head, cached per module under the
+    same key/refresh protocol as _mlp3_transpose_cache: (W1, W2) in
+    (out, in) layout — the FlatAdamW shadow views when the flat optimizer
+    owns the weights, a cast cache otherwise — and their (in, out)-major
+    transposes for the backward's dgrad products. Refreshed IN PLACE while
+    CAPTURE_REFRESH is set so a captured step's replays re-derive them
+    from the updated master weights."""
+    from .transformer import CAPTURE_REFRESH, _shadow_w16, _weights_epoch
+
+    s1, s2 = _shadow_w16(lin1.weight), _shadow_w16(lin2.weight)
+    key = (lin1.weight._version, lin2.weight._version, _weights_epoch[0],
+           s1 is not None, s2 is not None)
+    cache = getattr(lin1, "_dfa_nh_cache", None)
+    if cache is not None and cache[1]["w1t"].device != lin1.weight.device:
+        cache = None  # module moved after caching
+    if cache is not None and not CAPTURE_REFRESH[0] and cache[0] == key:
+        buf = cache[1]
+        return (s1 if s1 is not None else buf["w1"],
+                s2 if s2 is not None else buf["w2"], buf["w1t"], buf["w2t"])
+    bf = torch.bfloat16
+    if cache is None or cache[0][3:] != key[3:]:
+        dev = lin1.weight.device
+        buf = {
+            "w1t": torch.empty(lin1.weight.shape[::-1], dtype=bf, device=dev),
+            "w2t": torch.empty(lin2.weight.shape[::-1], dtype=bf, device=dev),
+        }
+        if s1 is None:
+            buf["w1"] = torch.empty(lin1.weight.shape, dtype=bf, device=dev)
+        if s2 is None:
+            buf["w2"] = torch.empty(lin2.weight.shape, dtype=bf, device=dev)
+    else:
+        buf = cache[1]
+    if s1 is None:
+        buf["w1"].copy_(lin1.weight.detach())
+    if s2 is None:
+        buf["w2"].copy_(lin2.weight.detach())
+    w1 = s1 if s1 is not None else buf["w1"]
+    w2 = s2 if s2 is not None else buf["w2"]
+    buf["w1t"].copy_(w1.t())
+    buf["w2t"].copy_(w2.t())
+    lin1._dfa_nh_cache = (key, buf)
+    return w1, w2, buf["w1t"], buf["w2t"]
+
+
+class _NodeHead(torch.autograd.Function):
+    """Fused node-level head (csrc/node_head.hip): split-A concat +
+    [Linear(256,256)+ReLU]x2 + Linear(256,1) over every node as ONE MFMA
+    kernel per direction. The weight grads reuse ext.wgrad (dW1 against the
+    [h|fe] tile image the forward materialises once, dW2 against H1) and
+    ext.colsum; dW3/db3 are folded into the backward kernel. On CPU the
+    fp32 torch reference (ops/reference.py) runs instead."""
+
+    @staticmethod
+    def forward(ctx, h, fe, w1, b1, w2, b2, w3, b3, w16):
+        ctx.nparams = (w1, b1, w2, b2, w3, b3)
+        ctx.d1 = h.shape[1]
+        if not h.is_cuda:
+            logits, x, h1, h2 = ref.node_head_fwd(h, fe, w1, b1, w2, b2, w3, b3)
+            ctx.save_for_backward(x, h1, h2, w1, w2, w3)
+            return logits
+        from ._ext import load_ext
+        from .transformer import _bias_f32
+
+        ext = load_ext(required=True)
+        w1_16, w2_16, w1t, w2t = w16
+        w3f = _bias_f32(w3).reshape(-1)
+        save = any(ctx.needs_input_grad)
+        outs = ext.node_head_fwd(
+            h.contiguous(), fe.contiguous(), w1_16, w2_16, _bias_f32(b1),
+            _bias_f32(b2), w3f, _bias_f32(b3), save=save,
+        )
+        if save:
+            _, x, h1, h2 = outs
+            ctx.save_for_backward(x, h1, h2, w1t, w2t, w3f)
+        return outs[0]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        ps = ctx.nparams
+        if not dlogits.is_cuda:
+            x, h1, h2, w1, w2, w3 = ctx.saved_tensors
+            grads = ref.node_head_bwd(dlogits, x, h1, h2, w1, w2, w3, ctx.d1)
+            return (*grads, None)
+        from ._ext import load_ext
+
+        ext = load_ext(required=True)
+        x, h1, h2, w1t, w2t, w3f = ctx.saved_tensors
+        dl = dlogits.float().contiguous()
+        direct = all(getattr(q, "_dfa_w16", None) is not None and q.grad is not None
+                     for q in ps)
+        if direct:
+            # every parameter grad accumulates in-kernel into the flat
+            # .grad views (atomic epilogues; a live .grad may already hold
+            # an earlier micro-batch's contribution)
+            w1, b1, w2, b2, w3, b3 = ps
+            dh, dfe, dh1, dh2, _, _ = ext.node_head_bwd(
+                dl, h1, h2, w1t, w2t, w3f, out_w3=w3.grad.view(-1), out_b3=b3.grad)
+            ext.wgrad(dh1, x, out=w1.grad)
+            ext.wgrad(dh2, h1, out=w2.grad)
+            ext.colsum(dh1, out=b1.grad)
+            ext.colsum(dh2, out=b2.grad)
+            return dh, dfe, None, None, None, None, None, None, None
+        dh, dfe, dh1, dh2, dW3, db3 = ext.node_head_bwd(dl, h1, h2, w1t, w2t, w3f)
+        grads = [ext.wgrad(dh1, x), ext.colsum(dh1), ext.wgrad(dh2, h1),
+                 ext.colsum(dh2), dW3.view_as(ps[4]), db3]
+        grads = [g if g.dtype == q.dtype else g.to(q.dtype) for g, q in zip(grads, ps)]
+        return (dh, dfe, *grads, None)
+
+
+def node_head(h, fe, lin1: torch.nn.Linear, lin2: torch.nn.Linear,
+              lin3: torch.nn.Linear):
+    """logits (N,) = lin3(relu(lin2(relu(lin1(cat([h, fe], -1)))))).squeeze(-1).
+    GPU: h, fe bf16 (N,128), all widths 256 (checked in the binding)."""
+    w16 = _node_head_cache(lin1, lin2) if h.is_cuda else None
+    return _NodeHead.apply(h, fe, lin1.weight, lin1.bias, lin2.weight, lin2.bias,
+                           lin3.weight, lin3.bias, w16)
+
+
 class _BCELogits(torch.autograd.Function):
     """Fused BCE-with-logits mean (optional pos_weight + per-graph weight
     mask): one kernel per direction vs torch's ~6-node chain at batch-256
@@ -485,6 +604,11 @@ class _BCELogits(torch.autograd.Function):
 
 
 def bce_with_logits(logits, labels, weight=None, pos_weight=None):
+    if weight is not None and weight.shape != logits.shape:
+        # the kernels index weight[i] for every logit
+        raise ValueError(
+            f"bce_with_logits: weight shape {tuple(weight.shape)} != logits "
+            f"shape {tuple(logits.shape)}")
     if logits.is_cuda:
         return _BCELogits.apply(logits, labels, weight, pos_weight)
     if weight is not None:

@@ -144,3 +144,35 @@ def segment_max(values: torch.Tensor, node_offsets: torch.Tensor) -> torch.Tenso
     out = torch.zeros(B, dtype=values.dtype, device=values.device)
     out.scatter_reduce_(0, seg, values, reduce="amax", include_self=False)
     return out
+
+
+# -- node-level head: [Linear(256,256)+ReLU]x2 + Linear(256,1) per node -------
+
+def node_head_fwd(
+    h: torch.Tensor, fe: torch.Tensor,
+    w1: torch.Tensor, b1: torch.Tensor,
+    w2: torch.Tensor, b2: torch.Tensor,
+    w3: torch.Tensor, b3: torch.Tensor,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """logits (N,), X = [h|fe], H1, H2 — equals
+    output_layer(cat([h, fe], -1)).squeeze(-1) with weights in nn.Linear
+    (out, in) layout; w3 is (1, D) or (D,)."""
+    x = torch.cat([h, fe], dim=-1)
+    h1 = torch.relu(x @ w1.t() + b1)
+    h2 = torch.relu(h1 @ w2.t() + b2)
+    logits = h2 @ w3.reshape(-1) + b3.reshape(())
+    return logits, x, h1, h2
+
+
+def node_head_bwd(
+    dlogits: torch.Tensor, x: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor,
+    w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, d1: int,
+):
+    """Returns (dh, dfe, dW1, db1, dW2, db2, dW3, db3); d1 = h's width."""
+    dh2 = (dlogits.unsqueeze(1) * w3.reshape(1, -1)) * (h2 > 0).to(h2.dtype)
+    dh1 = (dh2 @ w2) * (h1 > 0).to(h1.dtype)
+    dx = dh1 @ w1
+    dW3 = (h2.t() @ dlogits).reshape(w3.shape)
+    db3 = dlogits.sum().reshape(1)
+    return (dx[:, :d1], dx[:, d1:], dh1.t() @ x, dh1.sum(0), dh2.t() @ h1,
+            dh2.sum(0), dW3, db3)

@@ -173,8 +173,22 @@ class Trainer:
         else:
             ddp = DDPEngine(model)
         captured = None
+        self.n_capture_buckets = 0
+        # node-loss undersampling draws a data-dependent number of negatives
+        # per step (BaseModule.undersample_node_mask): not capturable
+        node_sampling = (
+            getattr(model, "label_style", None) == "node"
+            and getattr(model, "hparams", {}).get("undersample_node_on_loss_factor")
+            is not None
+        )
+        if node_sampling and self.graph_capture and self.device.type == "cuda":
+            logger.info(
+                "fit: undersample_node_on_loss_factor is set; running eager "
+                "steps (hipGraph step capture disabled)"
+            )
         if (
             self.graph_capture
+            and not node_sampling
             and self.accumulate_grad_batches == 1
             and ws == 1
             and self.device.type == "cuda"
@@ -316,6 +330,7 @@ class Trainer:
                 captured.steps - captured.eager_steps, captured.eager_steps,
                 len(captured.buckets),
             )
+            self.n_capture_buckets = len(captured.buckets)
         if ws > 1:
             import torch.distributed as dist
 

@@ -29,6 +29,7 @@ ext = CUDAExtension(
         "csrc/wgrad2.hip",
         "csrc/adamw.hip",
         "csrc/lmhead_ce.hip",
+        "csrc/node_head.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
