@@ -980,51 +980,78 @@ void launch_bce_logits_fwd(const float*, const float*, const float*, const float
 void launch_bce_logits_bwd(const float*, const float*, const float*, const float*,
                            const float*, const float*, float*, int, hipStream_t);
 
+// graph-level head (csrc/graph_head.hip)
+int gate_pool_num_chunks(int N);
 void launch_gate_pool_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const float*,
-                          const float*, const int*, __hip_bfloat16*, float*, int, int,
-                          int, hipStream_t);
+                          const float*, const int*, __hip_bfloat16*, float*, float*,
+                          int*, float*, float*, int, int, hipStream_t);
 void launch_gate_pool_bwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-                          const float*, const float*, const int*, __hip_bfloat16*,
-                          __hip_bfloat16*, float*, float*, float*, int, int, int,
+                          const float*, const float*, const float*, const int*,
+                          __hip_bfloat16*, __hip_bfloat16*, float*, float*, int, int,
                           hipStream_t);
 void launch_mlp3_fwd(const __hip_bfloat16*, const float*, const float*, const float*,
                      const float*, const float*, const float*, float*, float*, float*,
-                     int, int, hipStream_t);
+                     int, hipStream_t);
 void launch_mlp3_bwd(const float*, const float*, const float*, const float*, const float*,
-                     const float*, float*, float*, __hip_bfloat16*, int, int, hipStream_t);
+                     const float*, float*, float*, __hip_bfloat16*, int, hipStream_t);
 void launch_mlp3_wgrad(const __hip_bfloat16*, const float*, const float*, const float*,
                        const float*, const float*, float*, float*, float*, float*,
-                       float*, float*, int, int, hipStream_t);
+                       float*, float*, int, hipStream_t);
 
-// fused concat + gate linear + segment-softmax attention pool (flow-GNN head)
+// fused concat + gate linear + segment-softmax attention pool (flow-GNN head).
+// Returns {pooled bf16 (B,256), alpha fp32 (N), pooled fp32 (B,256), node ->
+// graph id int32 (N)}; the last two are for the backward, which takes its
+// per-graph dot from the fp32 row. A graph with no nodes gets a zero row.
 std::vector<at::Tensor> gate_pool_fwd(at::Tensor x1, at::Tensor x2, at::Tensor wg,
                                       at::Tensor bg, at::Tensor node_offsets) {
   CHECK_GPU(x1);
   CHECK_GPU(x2);
   TORCH_CHECK(x1.scalar_type() == at::kBFloat16 && x2.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(x1.is_contiguous() && x2.is_contiguous());
   TORCH_CHECK(wg.scalar_type() == at::kFloat && bg.scalar_type() == at::kFloat);
+  TORCH_CHECK(node_offsets.is_cuda() && node_offsets.scalar_type() == at::kInt &&
+              node_offsets.is_contiguous() && node_offsets.numel() >= 1);
   const int N = x1.size(0), D1 = x1.size(1), D = D1 + (int)x2.size(1);
   const int B = node_offsets.numel() - 1;
   TORCH_CHECK(x2.size(0) == N && wg.numel() == D);
   TORCH_CHECK(D == 256 && D1 == 128, "fused gate_pool is built for the "
               "128+128 concat geometry (vectorized lane mapping)");
+  auto fopt = x1.options().dtype(at::kFloat);
   auto out = at::empty({B, D}, x1.options());
-  auto alpha = at::empty({N}, x1.options().dtype(at::kFloat));
+  auto pooled32 = at::empty({B, D}, fopt);
+  auto alpha = at::empty({N}, fopt);
+  auto gid = at::empty({N}, x1.options().dtype(at::kInt));
+  const int nch = gate_pool_num_chunks(N);
+  auto ws_vec = at::empty({std::max(nch, 1) * 2, D}, fopt);
+  auto ws_ms = at::empty({std::max(nch, 1) * 2, 2}, fopt);
   launch_gate_pool_fwd(ptr<bf16_t>(x1), ptr<bf16_t>(x2), wg.data_ptr<float>(),
                        bg.data_ptr<float>(), node_offsets.data_ptr<int>(),
-                       mptr<bf16_t>(out), alpha.data_ptr<float>(), B, D1, D,
+                       mptr<bf16_t>(out), pooled32.data_ptr<float>(),
+                       alpha.data_ptr<float>(), gid.data_ptr<int>(),
+                       ws_vec.data_ptr<float>(), ws_ms.data_ptr<float>(), N, B,
                        cur_stream());
-  return {out, alpha};
+  return {out, alpha, pooled32, gid};
 }
 
 std::vector<at::Tensor> gate_pool_bwd(at::Tensor grad_out, at::Tensor x1, at::Tensor x2,
                                       at::Tensor wg, at::Tensor alpha,
-                                      at::Tensor node_offsets,
+                                      at::Tensor node_offsets, at::Tensor pooled32,
+                                      at::Tensor gid,
                                       c10::optional<at::Tensor> out_wg,
                                       c10::optional<at::Tensor> out_bg) {
   CHECK_GPU(grad_out);
   const int N = x1.size(0), D1 = x1.size(1), D = D1 + (int)x2.size(1);
   const int B = node_offsets.numel() - 1;
+  TORCH_CHECK(D == 256 && D1 == 128, "fused gate_pool is built for the "
+              "128+128 concat geometry (vectorized lane mapping)");
+  TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16 && grad_out.is_contiguous() &&
+              grad_out.size(0) == B && grad_out.size(1) == D);
+  TORCH_CHECK(pooled32.is_cuda() && pooled32.scalar_type() == at::kFloat &&
+              pooled32.is_contiguous() && pooled32.numel() == (long)B * D);
+  TORCH_CHECK(gid.is_cuda() && gid.scalar_type() == at::kInt && gid.is_contiguous() &&
+              gid.numel() == N);
+  TORCH_CHECK(alpha.scalar_type() == at::kFloat && alpha.numel() == N &&
+              wg.scalar_type() == at::kFloat && wg.numel() == D);
   auto gx1 = at::empty_like(x1);
   auto gx2 = at::empty_like(x2);
   at::Tensor dwg, dbg;
@@ -1037,31 +1064,34 @@ std::vector<at::Tensor> gate_pool_bwd(at::Tensor grad_out, at::Tensor x1, at::Te
     dwg = at::zeros({D}, x1.options().dtype(at::kFloat));
     dbg = at::zeros({1}, x1.options().dtype(at::kFloat));
   }
-  auto s_ws = at::empty({N}, x1.options().dtype(at::kFloat));
   launch_gate_pool_bwd(ptr<bf16_t>(grad_out), ptr<bf16_t>(x1), ptr<bf16_t>(x2),
                        wg.data_ptr<float>(), alpha.data_ptr<float>(),
-                       node_offsets.data_ptr<int>(), mptr<bf16_t>(gx1),
-                       mptr<bf16_t>(gx2), dwg.data_ptr<float>(), dbg.data_ptr<float>(),
-                       s_ws.data_ptr<float>(), B, D1, D, cur_stream());
+                       pooled32.data_ptr<float>(), gid.data_ptr<int>(),
+                       mptr<bf16_t>(gx1), mptr<bf16_t>(gx2), dwg.data_ptr<float>(),
+                       dbg.data_ptr<float>(), N, B, cur_stream());
   return {gx1, gx2, dwg, dbg};
 }
 
-// fused 3-layer MLP head forward: logits + relu activations (fp32 saves)
-std::vector<at::Tensor> mlp3_fwd(at::Tensor x, at::Tensor W1T, at::Tensor b1,
-                                 at::Tensor W2T, at::Tensor b2, at::Tensor W3,
+// fused 3-layer MLP head forward: logits + relu activations (fp32 saves).
+// W1/W2 are the master weights in their native (out, in) layout.
+std::vector<at::Tensor> mlp3_fwd(at::Tensor x, at::Tensor W1, at::Tensor b1,
+                                 at::Tensor W2, at::Tensor b2, at::Tensor W3,
                                  at::Tensor b3) {
   CHECK_GPU(x);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous());
   const int B = x.size(0), D = x.size(1);
-  TORCH_CHECK(D == 256 && W1T.size(0) == D && W3.numel() == D);
+  TORCH_CHECK(D == 256 && W1.numel() == (long)D * D && W2.numel() == (long)D * D &&
+              W3.numel() == D && b1.numel() == D && b2.numel() == D && b3.numel() == 1);
+  for (const at::Tensor* t : {&W1, &b1, &W2, &b2, &W3, &b3})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous());
   auto fopt = x.options().dtype(at::kFloat);
   auto h1 = at::empty({B, D}, fopt);
   auto h2 = at::empty({B, D}, fopt);
   auto logits = at::empty({B}, fopt);
-  launch_mlp3_fwd(ptr<bf16_t>(x), W1T.data_ptr<float>(), b1.data_ptr<float>(),
-                  W2T.data_ptr<float>(), b2.data_ptr<float>(), W3.data_ptr<float>(),
+  launch_mlp3_fwd(ptr<bf16_t>(x), W1.data_ptr<float>(), b1.data_ptr<float>(),
+                  W2.data_ptr<float>(), b2.data_ptr<float>(), W3.data_ptr<float>(),
                   b3.data_ptr<float>(), h1.data_ptr<float>(), h2.data_ptr<float>(),
-                  logits.data_ptr<float>(), B, D, cur_stream());
+                  logits.data_ptr<float>(), B, cur_stream());
   return {logits, h1, h2};
 }
 
@@ -1071,13 +1101,18 @@ std::vector<at::Tensor> mlp3_bwd(at::Tensor dlogits, at::Tensor x, at::Tensor h1
                                  c10::optional<std::vector<at::Tensor>> outs) {
   CHECK_GPU(dlogits);
   const int B = x.size(0), D = x.size(1);
+  TORCH_CHECK(D == 256 && x.scalar_type() == at::kBFloat16 && x.is_contiguous() &&
+              dlogits.scalar_type() == at::kFloat && dlogits.numel() == B &&
+              h1.numel() == (long)B * D && h2.numel() == (long)B * D);
+  for (const at::Tensor* t : {&W1, &W2, &W3})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous());
   auto fopt = x.options().dtype(at::kFloat);
   auto dh1 = at::empty({B, D}, fopt);
   auto dh2 = at::empty({B, D}, fopt);
   auto dx = at::empty_like(x);
   launch_mlp3_bwd(dlogits.data_ptr<float>(), h1.data_ptr<float>(), h2.data_ptr<float>(),
                   W1.data_ptr<float>(), W2.data_ptr<float>(), W3.data_ptr<float>(),
-                  dh1.data_ptr<float>(), dh2.data_ptr<float>(), mptr<bf16_t>(dx), B, D,
+                  dh1.data_ptr<float>(), dh2.data_ptr<float>(), mptr<bf16_t>(dx), B,
                   cur_stream());
   at::Tensor dW1, dW2, dW3, db1, db2, db3;
   if (outs.has_value()) {  // accumulate into the flat .grad views
@@ -1090,7 +1125,7 @@ std::vector<at::Tensor> mlp3_bwd(at::Tensor dlogits, at::Tensor x, at::Tensor h1
                 dW3.numel() == D && db1.numel() == D && db2.numel() == D &&
                 db3.numel() == 1);
   } else {
-    // the wgrad tail accumulates (+=) so every output starts zeroed
+    // the wgrad kernel accumulates (+=) so every output starts zeroed
     dW1 = at::zeros({D, D}, fopt);
     dW2 = at::zeros({D, D}, fopt);
     dW3 = at::zeros({1, D}, fopt);
@@ -1102,7 +1137,7 @@ std::vector<at::Tensor> mlp3_bwd(at::Tensor dlogits, at::Tensor x, at::Tensor h1
                     dh1.data_ptr<float>(), dh2.data_ptr<float>(),
                     dlogits.data_ptr<float>(), dW1.data_ptr<float>(),
                     dW2.data_ptr<float>(), dW3.data_ptr<float>(), db1.data_ptr<float>(),
-                    db2.data_ptr<float>(), db3.data_ptr<float>(), B, D, cur_stream());
+                    db2.data_ptr<float>(), db3.data_ptr<float>(), B, cur_stream());
   if (outs.has_value()) return {dx};
   return {dx, dW1, dW2, dW3, db1, db2, db3};
 }
@@ -1285,7 +1320,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gate_pool_fwd", &gate_pool_fwd);
   m.def("gate_pool_bwd", &gate_pool_bwd, pybind11::arg("grad_out"), pybind11::arg("x1"),
         pybind11::arg("x2"), pybind11::arg("wg"), pybind11::arg("alpha"),
-        pybind11::arg("node_offsets"), pybind11::arg("out_wg") = pybind11::none(),
+        pybind11::arg("node_offsets"), pybind11::arg("pooled32"), pybind11::arg("gid"),
+        pybind11::arg("out_wg") = pybind11::none(),
         pybind11::arg("out_bg") = pybind11::none());
   m.def("mlp3_fwd", &mlp3_fwd);
   m.def("mlp3_bwd", &mlp3_bwd, pybind11::arg("dlogits"), pybind11::arg("x"),

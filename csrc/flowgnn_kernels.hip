@@ -684,466 +684,8 @@ void launch_pack_gru_weights(const float* W_e, const float* b_e,
                      Wcat, WcatT, b_cat, W_eT, Wcat_perm, b_perm);
 }
 
-// ===========================================================================
-// Fused flow-GNN head (VERDICT round-1 item 4): the whole tail of the model
-// — concat([ggnn_out, feat_embed]) -> gate linear -> segment-softmax
-// attention pool -> 3-layer MLP -> logit — ran as ~11 forward + ~14
-// backward torch/hipBLASLt nodes at batch 256 (each 4-23 us of mostly
-// launch floor). Two fused kernels each way replace them:
-//   gate_pool_*: gate GEMV computed inline over the two concat halves,
-//     segment softmax + weighted segment sum (pool), with the gate-linear
-//     backward (dwg/dbg atomics) folded into the pool backward;
-//   mlp3_*: the [256->256 relu] x2 -> 256->1 head as one kernel per
-//     direction (weights read fp32 straight from the master params;
-//     forward uses cached transposes for coalesced reads), plus one
-//     weight-grad kernel covering all six parameter grads.
-// ===========================================================================
-
-// ---- gate + attention pool ----
-
-__global__ void gate_pool_fwd_kernel(
-    const __hip_bfloat16* __restrict__ x1, const __hip_bfloat16* __restrict__ x2,
-    const float* __restrict__ wg, const float* __restrict__ bg,
-    const int* __restrict__ node_offsets, __hip_bfloat16* __restrict__ out,
-    float* __restrict__ alpha, int D1, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* ws = reinterpret_cast<float*>(smem);  // D floats of wg
-  float* scratch = ws + D;                     // 8 floats
-  const int g = blockIdx.x;
-  const int lo = node_offsets[g], hi = node_offsets[g + 1];
-  const int n = hi - lo;
-  if (n <= 0) return;
-  for (int d = threadIdx.x; d < D; d += blockDim.x) ws[d] = wg[d];
-  __syncthreads();
-  const int D2 = D - D1;
-  // phase 0: per-node gate dot (wave per node, 2-node ILP), raw into alpha
-  const int wid = threadIdx.x / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int nw = blockDim.x / WAVE;
-  // vectorized gate dot: lane owns elements [4*lane, 4*lane+4) so lanes
-  // 0..31 read x1 and 32..63 read x2 as one 8-B load each (the scalar
-  // 2-B form was the kernel's dominant cost)
-  const int dv = 4 * lane;
-  const __hip_bfloat16* xs_half = (dv < D1) ? x1 : x2;
-  const int Ds_half = (dv < D1) ? D1 : D2;
-  const int dd_half = (dv < D1) ? dv : dv - D1;
-  for (int v = wid * 2; v < n; v += nw * 2) {
-    float s0 = 0.f, s1 = 0.f;
-    const bool has1 = (v + 1) < n;
-    {
-      __hip_bfloat16 a4[4];
-      *reinterpret_cast<uint2*>(a4) = *reinterpret_cast<const uint2*>(
-          xs_half + (long)(lo + v) * Ds_half + dd_half);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s0 += ws[dv + j] * to_f(a4[j]);
-      if (has1) {
-        *reinterpret_cast<uint2*>(a4) = *reinterpret_cast<const uint2*>(
-            xs_half + (long)(lo + v + 1) * Ds_half + dd_half);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s1 += ws[dv + j] * to_f(a4[j]);
-      }
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-      s0 += __shfl_down(s0, off);
-      s1 += __shfl_down(s1, off);
-    }
-    if (lane == 0) {
-      alpha[lo + v] = s0 + bg[0];
-      if (has1) alpha[lo + v + 1] = s1 + bg[0];
-    }
-  }
-  __syncthreads();
-  // phase A/B: segment softmax over alpha (raw gates -> probabilities)
-  float m = -3.4e38f;
-  for (int v = threadIdx.x; v < n; v += blockDim.x) m = fmaxf(m, alpha[lo + v]);
-  m = block_reduce(m, scratch, 0);
-  float s = 0.f;
-  for (int v = threadIdx.x; v < n; v += blockDim.x) {
-    const float e = __expf(alpha[lo + v] - m);
-    alpha[lo + v] = e;
-    s += e;
-  }
-  s = block_reduce(s, scratch, 1);
-  const float inv = 1.0f / s;
-  for (int v = threadIdx.x; v < n; v += blockDim.x) alpha[lo + v] *= inv;
-  __syncthreads();
-  // phase C: weighted segment sum over the two halves (8-way ILP)
-  for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    const __hip_bfloat16* xs = (d < D1) ? x1 : x2;
-    const int dd = (d < D1) ? d : d - D1;
-    const int Ds = (d < D1) ? D1 : D2;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f;
-    int v = 0;
-    for (; v + 8 <= n; v += 8) {
-      const long base = (long)(lo + v) * Ds + dd;
-      a0 += alpha[lo + v] * to_f(xs[base]);
-      a1 += alpha[lo + v + 1] * to_f(xs[base + Ds]);
-      a2 += alpha[lo + v + 2] * to_f(xs[base + 2 * Ds]);
-      a3 += alpha[lo + v + 3] * to_f(xs[base + 3 * Ds]);
-      a4 += alpha[lo + v + 4] * to_f(xs[base + 4 * Ds]);
-      a5 += alpha[lo + v + 5] * to_f(xs[base + 5 * Ds]);
-      a6 += alpha[lo + v + 6] * to_f(xs[base + 6 * Ds]);
-      a7 += alpha[lo + v + 7] * to_f(xs[base + 7 * Ds]);
-    }
-    for (; v < n; ++v) a0 += alpha[lo + v] * to_f(xs[(long)(lo + v) * Ds + dd]);
-    out[(long)g * D + d] =
-        from_f<__hip_bfloat16>(((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)));
-  }
-}
-
-__global__ void gate_pool_bwd_kernel(
-    const __hip_bfloat16* __restrict__ grad_out,
-    const __hip_bfloat16* __restrict__ x1, const __hip_bfloat16* __restrict__ x2,
-    const float* __restrict__ wg, const float* __restrict__ alpha,
-    const int* __restrict__ node_offsets, __hip_bfloat16* __restrict__ gx1,
-    __hip_bfloat16* __restrict__ gx2, float* __restrict__ dwg,
-    float* __restrict__ dbg, float* __restrict__ s_ws, int D1, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* go = reinterpret_cast<float*>(smem);  // D
-  float* ws = go + D;                          // D (wg)
-  float* dw = ws + D;                          // D (local dwg accum)
-  float* scratch = dw + D;                     // 8
-  const int g = blockIdx.x;
-  const int lo = node_offsets[g], hi = node_offsets[g + 1];
-  const int n = hi - lo;
-  if (n <= 0) return;
-  const int D2 = D - D1;
-  for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    go[d] = to_f(grad_out[(long)g * D + d]);
-    ws[d] = wg[d];
-    dw[d] = 0.f;
-  }
-  __syncthreads();
-  const int wid = threadIdx.x / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int nw = blockDim.x / WAVE;
-  // lane owns elements [4*lane, 4*lane+4): one 8-B load per node per pass
-  // (the scalar strided form was the kernel's dominant cost at 97 us),
-  // lanes 0..31 on the x1 half, 32..63 on x2
-  const int dv = 4 * lane;
-  const __hip_bfloat16* xs_half = (dv < D1) ? x1 : x2;
-  __hip_bfloat16* gxs_half = (dv < D1) ? gx1 : gx2;
-  const int Ds_half = (dv < D1) ? D1 : D2;
-  const int dd_half = (dv < D1) ? dv : dv - D1;
-  // pass 1: s_v = <go, x_v>
-  float local_dot = 0.f;
-  for (int v = wid * 2; v < n; v += nw * 2) {
-    float sv0 = 0.f, sv1 = 0.f;
-    const bool has1 = (v + 1) < n;
-    __hip_bfloat16 a4[4];
-    *reinterpret_cast<uint2*>(a4) = *reinterpret_cast<const uint2*>(
-        xs_half + (long)(lo + v) * Ds_half + dd_half);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sv0 += go[dv + j] * to_f(a4[j]);
-    if (has1) {
-      *reinterpret_cast<uint2*>(a4) = *reinterpret_cast<const uint2*>(
-          xs_half + (long)(lo + v + 1) * Ds_half + dd_half);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sv1 += go[dv + j] * to_f(a4[j]);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-      sv0 += __shfl_down(sv0, off);
-      sv1 += __shfl_down(sv1, off);
-    }
-    if (lane == 0) {
-      s_ws[lo + v] = sv0;
-      local_dot += alpha[lo + v] * sv0;
-      if (has1) {
-        s_ws[lo + v + 1] = sv1;
-        local_dot += alpha[lo + v + 1] * sv1;
-      }
-    }
-  }
-  __syncthreads();
-  const float dot = block_reduce(lane == 0 ? local_dot : 0.f, scratch, 1);
-  // pass 2: dx (pool + gate paths) as one 8-B store per node, dwg
-  // accumulated in registers (the per-(node,d) LDS atomics were serial)
-  float local_dbg = 0.f;
-  float ldw[4] = {};
-  for (int v = wid; v < n; v += nw) {
-    const float a = alpha[lo + v];
-    const float dgate = a * (s_ws[lo + v] - dot);
-    if (lane == 0) local_dbg += dgate;
-    __hip_bfloat16 a4[4], o4[4];
-    *reinterpret_cast<uint2*>(a4) = *reinterpret_cast<const uint2*>(
-        xs_half + (long)(lo + v) * Ds_half + dd_half);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xv = to_f(a4[j]);
-      o4[j] = from_f<__hip_bfloat16>(a * go[dv + j] + dgate * ws[dv + j]);
-      ldw[j] += dgate * xv;
-    }
-    *reinterpret_cast<uint2*>(gxs_half + (long)(lo + v) * Ds_half + dd_half) =
-        *reinterpret_cast<const uint2*>(o4);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (ldw[j] != 0.f) atomicAdd(&dw[dv + j], ldw[j]);
-  __syncthreads();
-  for (int d = threadIdx.x; d < D; d += blockDim.x)
-    if (dw[d] != 0.f) atomicAdd(&dwg[d], dw[d]);
-  const float bsum = block_reduce(lane == 0 ? local_dbg : 0.f, scratch, 1);
-  if (threadIdx.x == 0 && bsum != 0.f) atomicAdd(dbg, bsum);
-}
-
-void launch_gate_pool_fwd(const __hip_bfloat16* x1, const __hip_bfloat16* x2,
-                          const float* wg, const float* bg,
-                          const int* node_offsets, __hip_bfloat16* out,
-                          float* alpha, int B, int D1, int D,
-                          hipStream_t stream) {
-  const size_t lds = (D + 8) * sizeof(float);
-  if (B > 0)
-    hipLaunchKernelGGL(gate_pool_fwd_kernel, dim3(B), dim3(256), lds, stream,
-                       x1, x2, wg, bg, node_offsets, out, alpha, D1, D);
-}
-
-void launch_gate_pool_bwd(const __hip_bfloat16* grad_out, const __hip_bfloat16* x1,
-                          const __hip_bfloat16* x2, const float* wg,
-                          const float* alpha, const int* node_offsets,
-                          __hip_bfloat16* gx1, __hip_bfloat16* gx2, float* dwg,
-                          float* dbg, float* s_ws, int B, int D1, int D,
-                          hipStream_t stream) {
-  const size_t lds = (3 * D + 8) * sizeof(float);
-  if (B > 0)
-    hipLaunchKernelGGL(gate_pool_bwd_kernel, dim3(B), dim3(512), lds, stream,
-                       grad_out, x1, x2, wg, alpha, node_offsets, gx1, gx2,
-                       dwg, dbg, s_ws, D1, D);
-}
-
-// ---- 3-layer MLP head (256 -> 256 relu -> 256 relu -> 1) ----
-
-// RB rows per block: each weight load feeds RB independent FMA chains
-// (ILP breaks the serial accumulation latency; 4x fewer weight reads per
-// row) and the grid covers ceil(B/RB) blocks for occupancy.
-#define MLP_RB 4
-template <int RB>
-__global__ void mlp3_fwd_kernel(
-    const __hip_bfloat16* __restrict__ x, const float* __restrict__ W1T,
-    const float* __restrict__ b1, const float* __restrict__ W2T,
-    const float* __restrict__ b2, const float* __restrict__ W3,
-    const float* __restrict__ b3, float* __restrict__ h1,
-    float* __restrict__ h2, float* __restrict__ logits, int B, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* xs = reinterpret_cast<float*>(smem);  // RB * D
-  float* scratch = xs + RB * D;                // 8
-  const int j = threadIdx.x;
-  const int r0 = blockIdx.x * RB;
-  const int nr = min(RB, B - r0);
-  if (nr <= 0) return;
-  for (int r = 0; r < nr; ++r) xs[r * D + j] = to_f(x[(long)(r0 + r) * D + j]);
-  __syncthreads();
-  float a[RB];
-#pragma unroll
-  for (int r = 0; r < RB; ++r) a[r] = b1[j];
-  for (int d = 0; d < D; ++d) {
-    const float w = W1T[(long)d * D + j];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) a[r] += w * xs[r * D + d];
-  }
-  __syncthreads();
-  for (int r = 0; r < nr; ++r) {
-    const float v = fmaxf(a[r], 0.f);
-    h1[(long)(r0 + r) * D + j] = v;
-    xs[r * D + j] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < RB; ++r) a[r] = b2[j];
-  for (int d = 0; d < D; ++d) {
-    const float w = W2T[(long)d * D + j];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) a[r] += w * xs[r * D + d];
-  }
-  const float w3 = W3[j];
-  for (int r = 0; r < nr; ++r) {
-    const float v = fmaxf(a[r], 0.f);
-    h2[(long)(r0 + r) * D + j] = v;
-    const float z = block_reduce(w3 * v, scratch, 1);
-    if (j == 0) logits[r0 + r] = z + b3[0];
-  }
-}
-
-__global__ void mlp3_bwd_kernel(
-    const float* __restrict__ dlogits, const float* __restrict__ h1,
-    const float* __restrict__ h2, const float* __restrict__ W1,
-    const float* __restrict__ W2, const float* __restrict__ W3,
-    float* __restrict__ dh1, float* __restrict__ dh2,
-    __hip_bfloat16* __restrict__ dx, int B, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* ds = reinterpret_cast<float*>(smem);  // RB * D
-  const int j = threadIdx.x;
-  const int r0 = blockIdx.x * MLP_RB;
-  const int nr = min(MLP_RB, B - r0);
-  if (nr <= 0) return;
-  const float w3 = W3[j];
-  for (int r = 0; r < nr; ++r) {
-    const float g2 =
-        (h2[(long)(r0 + r) * D + j] > 0.f) ? dlogits[r0 + r] * w3 : 0.f;
-    dh2[(long)(r0 + r) * D + j] = g2;
-    ds[r * D + j] = g2;
-  }
-  __syncthreads();
-  float a[MLP_RB] = {};
-  for (int k = 0; k < D; ++k) {
-    const float w = W2[(long)k * D + j];
-#pragma unroll
-    for (int r = 0; r < MLP_RB; ++r) a[r] += w * ds[r * D + k];
-  }
-  __syncthreads();
-  for (int r = 0; r < nr; ++r) {
-    const float g1 = (h1[(long)(r0 + r) * D + j] > 0.f) ? a[r] : 0.f;
-    dh1[(long)(r0 + r) * D + j] = g1;
-    ds[r * D + j] = g1;
-  }
-  __syncthreads();
-  float c[MLP_RB] = {};
-  for (int k = 0; k < D; ++k) {
-    const float w = W1[(long)k * D + j];
-#pragma unroll
-    for (int r = 0; r < MLP_RB; ++r) c[r] += w * ds[r * D + k];
-  }
-  for (int r = 0; r < nr; ++r)
-    dx[(long)(r0 + r) * D + j] = from_f<__hip_bfloat16>(c[r]);
-}
-
-// all six parameter grads: dW1 = dh1^T pooled, dW2 = dh2^T h1,
-// dW3 = dlogits^T h2, db1/db2 column sums, db3 = sum(dlogits).
-// Tiled: each block owns a 16-wide i-block of one dW; the dh column block
-// is staged in LDS so every streamed x/h element feeds 16 FMAs (the naive
-// per-output form re-read 200 MB from L2 — 58 us measured).
-#define MW_IB 16
-#define MW_RCH 64  // rows per block chunk: 4 chunks at B=257 -> 129 blocks
-__global__ void mlp3_wgrad_kernel(
-    const __hip_bfloat16* __restrict__ x, const float* __restrict__ h1,
-    const float* __restrict__ h2, const float* __restrict__ dh1,
-    const float* __restrict__ dh2, const float* __restrict__ dlogits,
-    float* __restrict__ dW1, float* __restrict__ dW2, float* __restrict__ dW3,
-    float* __restrict__ db1, float* __restrict__ db2, float* __restrict__ db3,
-    int B, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dcol = reinterpret_cast<float*>(smem);  // [MW_RCH][MW_IB]
-  const int nb = D / MW_IB;
-  const int nrch = (B + MW_RCH - 1) / MW_RCH;
-  const int which = blockIdx.x / (nb * nrch);
-  if (which < 2) {
-    const int rem = blockIdx.x % (nb * nrch);
-    const int i0 = (rem % nb) * MW_IB;
-    const int r0 = (rem / nb) * MW_RCH;
-    const int r1 = min(B, r0 + MW_RCH);
-    const float* dh = which == 0 ? dh1 : dh2;
-    float* dW = which == 0 ? dW1 : dW2;
-    for (int t = threadIdx.x; t < (r1 - r0) * MW_IB; t += blockDim.x)
-      dcol[t] = dh[(long)(r0 + t / MW_IB) * D + i0 + (t % MW_IB)];
-    __syncthreads();
-    const int jj = threadIdx.x;
-    float acc[MW_IB] = {};
-    int r = r0;
-    // 4-deep load pipelining: per-iteration global latency was the bound
-    for (; r + 4 <= r1; r += 4) {
-      float xv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        xv[u] = which == 0 ? to_f(x[(long)(r + u) * D + jj])
-                           : h1[(long)(r + u) * D + jj];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float* dr = dcol + (r - r0 + u) * MW_IB;
-#pragma unroll
-        for (int i = 0; i < MW_IB; ++i) acc[i] += dr[i] * xv[u];
-      }
-    }
-    for (; r < r1; ++r) {
-      const float xv = which == 0 ? to_f(x[(long)r * D + jj])
-                                  : h1[(long)r * D + jj];
-      const float* dr = dcol + (r - r0) * MW_IB;
-#pragma unroll
-      for (int i = 0; i < MW_IB; ++i) acc[i] += dr[i] * xv;
-    }
-    // ALWAYS accumulate: dW may be a live flat .grad view (direct-grad
-    // mode) carrying an earlier micro-batch's contribution — a plain
-    // store at nrch==1 dropped it (caught by the 2x-accumulation test)
-#pragma unroll
-    for (int i = 0; i < MW_IB; ++i)
-      atomicAdd(&dW[(long)(i0 + i) * D + jj], acc[i]);
-    return;
-  }
-  // tail blocks: dW3 + biases, one output per thread across 4 blocks,
-  // 4 independent accumulation chains each (a single serial-chain tail
-  // block was the whole kernel's critical path)
-  const int tb = blockIdx.x - 2 * nb * nrch;
-  const int o = tb * (int)blockDim.x + threadIdx.x;
-  if (o > 3 * D) return;
-  const float* srcs[3] = {h2, dh1, dh2};
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (o < D) {
-    int r = 0;
-    for (; r + 4 <= B; r += 4) {
-      s0 += dlogits[r] * h2[(long)r * D + o];
-      s1 += dlogits[r + 1] * h2[(long)(r + 1) * D + o];
-      s2 += dlogits[r + 2] * h2[(long)(r + 2) * D + o];
-      s3 += dlogits[r + 3] * h2[(long)(r + 3) * D + o];
-    }
-    for (; r < B; ++r) s0 += dlogits[r] * h2[(long)r * D + o];
-    dW3[o] += (s0 + s1) + (s2 + s3);  // accumulate: out may be a live .grad
-  } else if (o < 3 * D) {
-    const float* src = srcs[o / D];
-    const int jj = o % D;
-    int r = 0;
-    for (; r + 4 <= B; r += 4) {
-      s0 += src[(long)r * D + jj];
-      s1 += src[(long)(r + 1) * D + jj];
-      s2 += src[(long)(r + 2) * D + jj];
-      s3 += src[(long)(r + 3) * D + jj];
-    }
-    for (; r < B; ++r) s0 += src[(long)r * D + jj];
-    float* dst = (o < 2 * D) ? db1 : db2;
-    dst[jj] += (s0 + s1) + (s2 + s3);
-  } else {
-    for (int r = 0; r < B; ++r) s0 += dlogits[r];
-    db3[0] += s0;
-  }
-}
-
-
-void launch_mlp3_fwd(const __hip_bfloat16* x, const float* W1T, const float* b1,
-                     const float* W2T, const float* b2, const float* W3,
-                     const float* b3, float* h1, float* h2, float* logits,
-                     int B, int D, hipStream_t stream) {
-  // RB=2 doubles the block count (B=257 -> 129): in a captured stream the
-  // kernel runs alone, so grid width beats per-thread load reuse
-  constexpr int RB = 2;
-  const int blocks = (B + RB - 1) / RB;
-  const size_t lds = (RB * D + 8) * sizeof(float);
-  if (B > 0)
-    hipLaunchKernelGGL(mlp3_fwd_kernel<RB>, dim3(blocks), dim3(D), lds, stream,
-                       x, W1T, b1, W2T, b2, W3, b3, h1, h2, logits, B, D);
-}
-
-void launch_mlp3_bwd(const float* dlogits, const float* h1, const float* h2,
-                     const float* W1, const float* W2, const float* W3,
-                     float* dh1, float* dh2, __hip_bfloat16* dx, int B, int D,
-                     hipStream_t stream) {
-  const int blocks = (B + MLP_RB - 1) / MLP_RB;
-  const size_t lds = (MLP_RB * D) * sizeof(float);
-  if (B > 0)
-    hipLaunchKernelGGL(mlp3_bwd_kernel, dim3(blocks), dim3(D), lds, stream,
-                       dlogits, h1, h2, W1, W2, W3, dh1, dh2, dx, B, D);
-}
-
-void launch_mlp3_wgrad(const __hip_bfloat16* x, const float* h1, const float* h2,
-                       const float* dh1, const float* dh2, const float* dlogits,
-                       float* dW1, float* dW2, float* dW3, float* db1,
-                       float* db2, float* db3, int B, int D,
-                       hipStream_t stream) {
-  const int nb = D / MW_IB;
-  const int nrch = (B + MW_RCH - 1) / MW_RCH;
-  const size_t lds = (size_t)MW_RCH * MW_IB * sizeof(float);
-  // dW1/dW2 must be ZEROED by the caller when nrch > 1 (atomic epilogue)
-  const int tail_blocks = (3 * D + 1 + D - 1) / D + 1;
-  hipLaunchKernelGGL(mlp3_wgrad_kernel, dim3(2 * nb * nrch + tail_blocks),
-                     dim3(D), lds, stream, x, h1, h2, dh1, dh2, dlogits, dW1,
-                     dW2, dW3, db1, db2, db3, B, D);
-}
+// The graph-level head (gate + attention pool, 3-layer MLP) lives in
+// csrc/graph_head.hip.
 
 // Fused BCE-with-logits (mean over weighted graphs) + backward seed. The
 // torch chain (binary_cross_entropy_with_logits fwd + mean + backward's

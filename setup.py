@@ -30,6 +30,7 @@ ext = CUDAExtension(
         "csrc/adamw.hip",
         "csrc/lmhead_ce.hip",
         "csrc/node_head.hip",
+        "csrc/graph_head.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
