@@ -537,8 +537,12 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
     gW_e = at::zeros({H, H}, opts.dtype(at::kFloat));
     cs_e = at::zeros({H}, opts.dtype(at::kFloat));
   }
-  launch_wgrad2(ptr<bf16_t>(A_w), ptr<bf16_t>(HH), gW_e.data_ptr<float>(),
-                cs_e.data_ptr<float>(), S * N, H, H, acc_we ? 1 : 0, stream);
+  if (H % 128 == 0)
+    launch_wgrad2(ptr<bf16_t>(A_w), ptr<bf16_t>(HH), gW_e.data_ptr<float>(),
+                  cs_e.data_ptr<float>(), S * N, H, H, acc_we ? 1 : 0, stream);
+  else  // wgrad2 needs 128-aligned M and C; the generic kernel is bounds-checked
+    launch_wgrad(ptr<bf16_t>(A_w), ptr<bf16_t>(HH), nullptr, gW_e.data_ptr<float>(),
+                 cs_e.data_ptr<float>(), S * N, H, H, H, stream);
   if (gru_direct) {  // grads already accumulated in the flat views
     auto none = at::empty({0}, opts.dtype(at::kFloat));
     return {grad_h, gW_e, cs_e, none, none, none, none};
@@ -569,6 +573,29 @@ std::vector<at::Tensor> gru_gates2_fwd(at::Tensor gicat, at::Tensor h) {
                              mptr<T>(n), mptr<T>(hn), N * H, H, cur_stream());
   });
   return {h_new, r, z, n, hn};
+}
+
+// stand-alone entry to the gate backward the fused loop launches per step
+// (unit tests); returns {grad_gicat (N, 4H), grad_h_direct (N, H)}
+std::vector<at::Tensor> gru_gates2_bwd(at::Tensor grad_h_new, at::Tensor h, at::Tensor r,
+                                       at::Tensor z, at::Tensor n, at::Tensor hn) {
+  CHECK_GPU(grad_h_new);
+  CHECK_GPU(h);
+  const long N = h.size(0);
+  const int H = h.size(1);
+  for (const at::Tensor* t : {&grad_h_new, &r, &z, &n, &hn})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->sizes() == h.sizes() &&
+                    t->scalar_type() == h.scalar_type(),
+                "gru_gates2_bwd: operands must match h");
+  auto grad_gicat = at::empty({N, 4 * H}, h.options());
+  auto grad_h = at::empty_like(h);
+  dispatch_float_bf16(h, "gru_gates2_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    launch_gru_gates2_bwd<T>(ptr<T>(grad_h_new), ptr<T>(h), ptr<T>(r), ptr<T>(z), ptr<T>(n),
+                             ptr<T>(hn), mptr<T>(grad_gicat), mptr<T>(grad_h), N * H, H,
+                             cur_stream());
+  });
+  return {grad_gicat, grad_h};
 }
 
 at::Tensor colsum(at::Tensor x, c10::optional<at::Tensor> out_opt) {
@@ -1289,6 +1316,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad", &wgrad, pybind11::arg("A"), pybind11::arg("B"),
         pybind11::arg("out") = pybind11::none());
   m.def("gru_gates2_fwd", &gru_gates2_fwd);
+  m.def("gru_gates2_bwd", &gru_gates2_bwd);
   m.def("colsum", &colsum, pybind11::arg("x"), pybind11::arg("out") = pybind11::none());
   m.def("ggnn_fused_fwd", &ggnn_fused_fwd);
   m.def("pack_gru_weights", &pack_gru_weights);

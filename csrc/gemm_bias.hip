@@ -37,7 +37,10 @@ __device__ __forceinline__ int swz(int row, int byte) {
 // BMT = 64 normally; 32 when the 64-row grid would underfill 256 CUs —
 // these GNN GEMMs are HBM-latency-bound at ~0.7 waves/SIMD (PMC: WAIT_ANY
 // 73% of wave cycles), so doubling the block count is the lever
-template <int BMT>
+// CT (column tail): COL is not a multiple of BN (the GGNN W_e GEMMs at
+// H = 64 or 192) — W rows and output columns past COL are masked. The
+// 128-aligned instantiations compile without the checks.
+template <int BMT, bool CT = false>
 __global__ __launch_bounds__(256) void gemm_bias_kernel(
     const bf16* __restrict__ A1, const bf16* __restrict__ A2,
     const bf16* __restrict__ W, const bf16* __restrict__ bias,
@@ -83,6 +86,10 @@ __global__ __launch_bounds__(256) void gemm_bias_kernel(
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int rr = srow + p * 32;
+      if constexpr (CT) {
+        br[p] = {};
+        if (c0 + rr >= COL) continue;
+      }
       br[p] = *reinterpret_cast<const uint4v*>(W + (long)(c0 + rr) * K + kk +
                                                soff / 2);
     }
@@ -147,6 +154,9 @@ __global__ __launch_bounds__(256) void gemm_bias_kernel(
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const int col = c0 + wn * 64 + n * 16 + (lane & 15);
+      if constexpr (CT) {
+        if (col >= COL) continue;
+      }
       const float b = bias ? __bfloat162float(bias[col]) : 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -166,6 +176,14 @@ void launch_gemm_bias2(const bf16* A1, const bf16* A2, const bf16* W,
                        const bf16* bias, const bf16* addend, long astride,
                        const bf16* addend2, long astride2, bf16* out, int N,
                        int K, int K1, int COL, hipStream_t stream) {
+  if (COL % BN != 0) {  // column-tail variant, 32-row tile only
+    const dim3 grid((N + 31) / 32, (COL + BN - 1) / BN);
+    const size_t lds = 2 * (32 + BN) * ROWB;
+    hipLaunchKernelGGL((gemm_bias_kernel<32, true>), grid, dim3(256), lds,
+                       stream, A1, A2, W, bias, addend, astride, addend2,
+                       astride2, out, N, K, K1, COL);
+    return;
+  }
   const long blocks64 = (long)((N + BM - 1) / BM) * (COL / BN);
   if (blocks64 < 384) {
     const dim3 grid((N + 31) / 32, COL / BN);
