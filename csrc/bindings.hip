@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <c10/hip/HIPStream.h>
+#include <c10/util/accumulate.h>
 
 // the launchers are defined (at global scope) in flowgnn_kernels.hip
 template <typename T>
@@ -137,6 +138,18 @@ void dispatch_float_bf16(const at::Tensor& t, const char* name, F&& f) {
   }
 }
 
+// fp32 gradient accumulator of an op: `out` when given — a live flat .grad
+// view (parallel/optim.py) the kernel ADDS into — else fresh zeros.
+static at::Tensor acc_or_zeros(const c10::optional<at::Tensor>& out, at::IntArrayRef shape,
+                               const at::TensorOptions& like, const char* name) {
+  if (!out.has_value()) return at::zeros(shape, like.dtype(at::kFloat));
+  TORCH_CHECK(out->is_cuda() && out->scalar_type() == at::kFloat && out->is_contiguous() &&
+                  out->numel() == c10::multiply_integers(shape),
+              name, ": accumulator must be a contiguous fp32 GPU tensor of ",
+              c10::multiply_integers(shape), " elements");
+  return *out;
+}
+
 template <typename T>
 const T* ptr(const at::Tensor& t) {
   return reinterpret_cast<const T*>(t.data_ptr());
@@ -175,15 +188,8 @@ at::Tensor embed4_bwd(at::Tensor grad_out, at::Tensor idx, long V, long Demb,
   CHECK_GPU(grad_out);
   CHECK_GPU(idx);
   TORCH_CHECK(Demb == 32, "Demb must be 32");
-  at::Tensor grad;
-  const bool acc = out_opt.has_value();
-  if (acc) {  // accumulate into the flat .grad region of the 4 tables
-    grad = *out_opt;
-    TORCH_CHECK(grad.is_cuda() && grad.scalar_type() == at::kFloat &&
-                grad.is_contiguous() && grad.numel() == 4 * V * Demb);
-  } else {
-    grad = at::zeros({4, V, Demb}, grad_out.options().dtype(at::kFloat));
-  }
+  const bool acc = out_opt.has_value();  // the flat .grad region of the 4 tables
+  auto grad = acc_or_zeros(out_opt, {4, V, Demb}, grad_out.options(), "embed4_bwd");
   const long total = grad_out.numel();
   dispatch_float_bf16(grad_out, "embed4_bwd", [&](auto tag) {
     using T = decltype(tag);
@@ -311,17 +317,6 @@ at::Tensor segment_max(at::Tensor values, at::Tensor node_offsets) {
 
 using bf16_t = __hip_bfloat16;
 
-static at::Tensor build_wcat(const at::Tensor& W_ih, const at::Tensor& W_hh, long H) {
-  auto Wcat = at::zeros({4 * H, 2 * H}, W_ih.options());
-  Wcat.narrow(0, 0, H).narrow(1, 0, H).copy_(W_ih.narrow(0, 0, H));
-  Wcat.narrow(0, 0, H).narrow(1, H, H).copy_(W_hh.narrow(0, 0, H));
-  Wcat.narrow(0, H, H).narrow(1, 0, H).copy_(W_ih.narrow(0, H, H));
-  Wcat.narrow(0, H, H).narrow(1, H, H).copy_(W_hh.narrow(0, H, H));
-  Wcat.narrow(0, 2 * H, H).narrow(1, 0, H).copy_(W_ih.narrow(0, 2 * H, H));
-  Wcat.narrow(0, 3 * H, H).narrow(1, H, H).copy_(W_hh.narrow(0, 2 * H, H));
-  return Wcat;
-}
-
 at::Tensor gemm_bias(at::Tensor A, at::Tensor W, c10::optional<at::Tensor> bias,
                      c10::optional<at::Tensor> addend) {
   CHECK_GPU(A);
@@ -355,24 +350,16 @@ at::Tensor wgrad(at::Tensor A, at::Tensor B, c10::optional<at::Tensor> out_opt) 
   const int K = A.size(0), M = A.size(1), C = B.size(1);
   TORCH_CHECK(B.size(0) == K && M % 64 == 0 && C % 8 == 0);
   const bool acc = out_opt.has_value();
-  at::Tensor out;
-  if (acc) {
-    out = *out_opt;
-    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
-                out.is_contiguous() && out.numel() == (long)M * C,
-                "wgrad out must be a contiguous fp32 (M, C) accumulator");
-  }
+  // always zero-init: whether the launcher plain-stores (one K chunk) or
+  // atomically accumulates (split K) is ITS decision — duplicating the
+  // chunking math here to pick empty-vs-zeros risked an uninitialized
+  // accumulator if the two ever diverged (they did differ by K-floor)
+  auto out = acc_or_zeros(out_opt, {M, C}, A.options(), "wgrad");
   if (M % 128 == 0 && C % 128 == 0) {  // wgrad2 zero-fills K tails
-    // always zero-init: whether the launcher plain-stores (one K chunk) or
-    // atomically accumulates (split K) is ITS decision — duplicating the
-    // chunking math here to pick empty-vs-zeros risked an uninitialized
-    // accumulator if the two ever diverged (they did differ by K-floor)
-    if (!acc) out = at::zeros({M, C}, A.options().dtype(at::kFloat));
     launch_wgrad2(ptr<bf16_t>(A), ptr<bf16_t>(B), out.data_ptr<float>(), nullptr,
                   K, M, C, acc ? 1 : 0, cur_stream());
     return out;
   }
-  if (!acc) out = at::zeros({M, C}, A.options().dtype(at::kFloat));
   launch_wgrad(ptr<bf16_t>(A), ptr<bf16_t>(B), nullptr, out.data_ptr<float>(), nullptr,
                K, M, C, C, cur_stream());
   return out;
@@ -524,19 +511,10 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
     launch_wgrad(ptr<bf16_t>(A_g), ptr<bf16_t>(M), ptr<bf16_t>(HH), gWcat.data_ptr<float>(),
                  cs4.data_ptr<float>(), S * N, 4 * H, 2 * H, H, stream);
   auto A_w = Gwh.view({S * N, H});
-  at::Tensor gW_e, cs_e;
-  const bool acc_we = out_we.has_value();
-  if (acc_we) {  // accumulate W_e/b_e grads into the flat .grad views
-    gW_e = *out_we;
-    cs_e = *out_be;
-    TORCH_CHECK(gW_e.is_cuda() && gW_e.scalar_type() == at::kFloat &&
-                gW_e.is_contiguous() && gW_e.numel() == H * H &&
-                cs_e.is_cuda() && cs_e.scalar_type() == at::kFloat &&
-                cs_e.numel() == H);
-  } else {
-    gW_e = at::zeros({H, H}, opts.dtype(at::kFloat));
-    cs_e = at::zeros({H}, opts.dtype(at::kFloat));
-  }
+  const bool acc_we = out_we.has_value();  // W_e/b_e grads into the flat .grad views
+  TORCH_CHECK(out_be.has_value() == acc_we, "ggnn_fused_bwd: out_we and out_be go together");
+  auto gW_e = acc_or_zeros(out_we, {H, H}, opts, "ggnn_fused_bwd out_we");
+  auto cs_e = acc_or_zeros(out_be, {H}, opts, "ggnn_fused_bwd out_be");
   if (H % 128 == 0)
     launch_wgrad2(ptr<bf16_t>(A_w), ptr<bf16_t>(HH), gW_e.data_ptr<float>(),
                   cs_e.data_ptr<float>(), S * N, H, H, acc_we ? 1 : 0, stream);
@@ -600,14 +578,7 @@ std::vector<at::Tensor> gru_gates2_bwd(at::Tensor grad_h_new, at::Tensor h, at::
 
 at::Tensor colsum(at::Tensor x, c10::optional<at::Tensor> out_opt) {
   CHECK_GPU(x);
-  at::Tensor out;
-  if (out_opt.has_value()) {  // accumulate into the flat .grad view (atomic)
-    out = *out_opt;
-    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
-                out.is_contiguous() && out.numel() == x.size(1));
-  } else {
-    out = at::zeros({x.size(1)}, x.options().dtype(at::kFloat));
-  }
+  auto out = acc_or_zeros(out_opt, {x.size(1)}, x.options(), "colsum");
   dispatch_float_bf16(x, "colsum", [&](auto tag) {
     using T = decltype(tag);
     launch_colsum<T>(ptr<T>(x), out.data_ptr<float>(), x.size(0), x.size(1), cur_stream());
@@ -779,14 +750,7 @@ at::Tensor rmsnorm_wgrad(at::Tensor dy, at::Tensor x, at::Tensor rstd,
                          c10::optional<at::Tensor> out_opt) {
   const int D = x.size(-1);
   const long N = x.numel() / D;
-  at::Tensor dgamma;
-  if (out_opt.has_value()) {  // accumulate into the flat .grad view (atomic)
-    dgamma = *out_opt;
-    TORCH_CHECK(dgamma.is_cuda() && dgamma.scalar_type() == at::kFloat &&
-                dgamma.is_contiguous() && dgamma.numel() == D);
-  } else {
-    dgamma = at::zeros({D}, x.options().dtype(at::kFloat));
-  }
+  auto dgamma = acc_or_zeros(out_opt, {D}, x.options(), "rmsnorm_wgrad");
   dispatch_float_bf16(x, "rmsnorm_wgrad", [&](auto tag) {
     using T = decltype(tag);
     launch_rmsnorm_wgrad<T>(ptr<T>(dy), ptr<T>(x), rstd.data_ptr<float>(),
@@ -1081,16 +1045,10 @@ std::vector<at::Tensor> gate_pool_bwd(at::Tensor grad_out, at::Tensor x1, at::Te
               wg.scalar_type() == at::kFloat && wg.numel() == D);
   auto gx1 = at::empty_like(x1);
   auto gx2 = at::empty_like(x2);
-  at::Tensor dwg, dbg;
-  if (out_wg.has_value()) {  // accumulate into the flat .grad views (atomic)
-    dwg = *out_wg;
-    dbg = *out_bg;
-    TORCH_CHECK(dwg.is_cuda() && dwg.scalar_type() == at::kFloat && dwg.numel() == D &&
-                dbg.is_cuda() && dbg.scalar_type() == at::kFloat && dbg.numel() == 1);
-  } else {
-    dwg = at::zeros({D}, x1.options().dtype(at::kFloat));
-    dbg = at::zeros({1}, x1.options().dtype(at::kFloat));
-  }
+  TORCH_CHECK(out_wg.has_value() == out_bg.has_value(),
+              "gate_pool_bwd: out_wg and out_bg go together");
+  auto dwg = acc_or_zeros(out_wg, {D}, x1.options(), "gate_pool_bwd out_wg");
+  auto dbg = acc_or_zeros(out_bg, {1}, x1.options(), "gate_pool_bwd out_bg");
   launch_gate_pool_bwd(ptr<bf16_t>(grad_out), ptr<bf16_t>(x1), ptr<bf16_t>(x2),
                        wg.data_ptr<float>(), alpha.data_ptr<float>(),
                        pooled32.data_ptr<float>(), gid.data_ptr<int>(),
@@ -1141,25 +1099,16 @@ std::vector<at::Tensor> mlp3_bwd(at::Tensor dlogits, at::Tensor x, at::Tensor h1
                   W1.data_ptr<float>(), W2.data_ptr<float>(), W3.data_ptr<float>(),
                   dh1.data_ptr<float>(), dh2.data_ptr<float>(), mptr<bf16_t>(dx), B,
                   cur_stream());
-  at::Tensor dW1, dW2, dW3, db1, db2, db3;
-  if (outs.has_value()) {  // accumulate into the flat .grad views
-    TORCH_CHECK(outs->size() == 6, "outs = [dW1, db1, dW2, db2, dW3, db3]");
-    dW1 = (*outs)[0]; db1 = (*outs)[1]; dW2 = (*outs)[2];
-    db2 = (*outs)[3]; dW3 = (*outs)[4]; db3 = (*outs)[5];
-    for (auto& t : *outs)
-      TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous());
-    TORCH_CHECK(dW1.numel() == (long)D * D && dW2.numel() == (long)D * D &&
-                dW3.numel() == D && db1.numel() == D && db2.numel() == D &&
-                db3.numel() == 1);
-  } else {
-    // the wgrad kernel accumulates (+=) so every output starts zeroed
-    dW1 = at::zeros({D, D}, fopt);
-    dW2 = at::zeros({D, D}, fopt);
-    dW3 = at::zeros({1, D}, fopt);
-    db1 = at::zeros({D}, fopt);
-    db2 = at::zeros({D}, fopt);
-    db3 = at::zeros({1}, fopt);
-  }
+  // the wgrad kernel accumulates (+=): into the flat .grad views when given
+  // (outs = [dW1, db1, dW2, db2, dW3, db3]), else into fresh zeros
+  TORCH_CHECK(!outs.has_value() || outs->size() == 6, "mlp3_bwd: outs takes 6 tensors");
+  auto acc = [&](int i, at::IntArrayRef shape) {
+    c10::optional<at::Tensor> out;
+    if (outs.has_value()) out = (*outs)[i];
+    return acc_or_zeros(out, shape, fopt, "mlp3_bwd outs");
+  };
+  auto dW1 = acc(0, {D, D}), dW2 = acc(2, {D, D}), dW3 = acc(4, {1, D});
+  auto db1 = acc(1, {D}), db2 = acc(3, {D}), db3 = acc(5, {1});
   launch_mlp3_wgrad(ptr<bf16_t>(x), h1.data_ptr<float>(), h2.data_ptr<float>(),
                     dh1.data_ptr<float>(), dh2.data_ptr<float>(),
                     dlogits.data_ptr<float>(), dW1.data_ptr<float>(),
@@ -1248,19 +1197,8 @@ std::vector<at::Tensor> node_head_bwd(at::Tensor dlogits, at::Tensor H1, at::Ten
   check_node_head_w(W2T, "W2T");
   check_node_head_v(w3, 256, "w3");
   auto fopt = H1.options().dtype(at::kFloat);
-  at::Tensor dW3, db3;
-  if (out_w3.has_value()) {
-    dW3 = *out_w3;
-    check_node_head_v(dW3, 256, "out_w3");
-  } else {
-    dW3 = at::zeros({1, 256}, fopt);
-  }
-  if (out_b3.has_value()) {
-    db3 = *out_b3;
-    check_node_head_v(db3, 1, "out_b3");
-  } else {
-    db3 = at::zeros({1}, fopt);
-  }
+  auto dW3 = acc_or_zeros(out_w3, {1, 256}, fopt, "node_head_bwd out_w3");
+  auto db3 = acc_or_zeros(out_b3, {1}, fopt, "node_head_bwd out_b3");
   auto dH1 = at::empty_like(H1);
   auto dH2 = at::empty_like(H2);
   auto dh = at::empty({N, 128}, H1.options());
@@ -1494,14 +1432,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(idx.scalar_type() == at::kLong && idx.is_contiguous());
     const int D = dY.size(-1);
     const long N = dY.numel() / D;
-    at::Tensor dW;
-    if (out_opt.has_value()) {  // accumulate into the flat .grad view (atomic)
-      dW = *out_opt;
-      TORCH_CHECK(dW.is_cuda() && dW.scalar_type() == at::kFloat &&
-                  dW.is_contiguous() && dW.numel() == num_rows * (long)D);
-    } else {
-      dW = at::zeros({num_rows, (long)D}, dY.options().dtype(at::kFloat));
-    }
+    auto dW = acc_or_zeros(out_opt, {num_rows, (long)D}, dY.options(), "embed_scatter");
     dispatch_float_bf16(dY, "embed_scatter", [&](auto tag) {
       using T = decltype(tag);
       launch_embed_scatter<T>(ptr<T>(dY), idx.data_ptr<long>(),

@@ -2,10 +2,12 @@
 
 Each op is a torch.autograd.Function that dispatches to the hand-written
 HIP/CDNA4 kernel on GPU (required — no eager fallback on GPU) and to the
-fp32 torch reference on CPU. GEMMs that are plain library GEMMs (the GRU's
-input/hidden projections, the MLP) go through torch.matmul (rocBLAS /
-hipBLASLt on ROCm); everything irregular (gather, segment ops, fused gates)
-is a custom kernel.
+fp32 torch reference on CPU. On GPU under bf16 the whole GGNN loop
+(ggnn_fused) and both heads (gate_pool + mlp3, node_head) run on the
+hand-written MFMA kernels, as do the gathers and segment ops; only the
+op-by-op fp32 route (gru_cell, the numerics path) sends its GRU projections
+through torch.matmul. Derived-weight caches and direct gradient
+accumulation follow ops/_weights.py.
 """
 
 from __future__ import annotations
@@ -15,7 +17,8 @@ from typing import Optional
 import torch
 
 from . import reference as ref
-from ._ext import ext_for
+from ._ext import ext_for, load_ext
+from ._weights import _bias_f32, _shadow_w16, derived, direct_grads, packed_shadow
 
 
 class _Embed4(torch.autograd.Function):
@@ -85,18 +88,11 @@ def embed4_direct_view(ws):
     weights' optimizer shadow, or None when unavailable (no flat optimizer,
     non-adjacent tables, or CPU). Syncs each table's shadow first so a
     torch-level write (checkpoint load) is reflected (_shadow_w16)."""
-    from .transformer import _shadow_w16
-
-    if any(_shadow_w16(w) is None or w.grad is None for w in ws):
-        return None
-    base = ws[0]._dfa_w16_base
-    off = ws[0]._dfa_w16_off
     n = ws[0].numel()
-    for i, w in enumerate(ws):
-        if (w._dfa_w16_base is not base or w._dfa_w16_off != off + i * n
-                or w.numel() != n or w.shape[-1] != 32):
-            return None
-    return base[off : off + 4 * n].view(4, ws[0].shape[0], 32)
+    if any(w.numel() != n or w.shape[-1] != 32 for w in ws) or not direct_grads(*ws):
+        return None
+    flat = packed_shadow(ws)
+    return None if flat is None else flat.view(4, ws[0].shape[0], 32)
 
 
 def embed4_direct(ws, idx):
@@ -192,42 +188,28 @@ def _ggnn_pack_cache(linear: torch.nn.Linear, gru: torch.nn.GRUCell):
     (csrc/flowgnn_kernels.hip pack_gru_weights) under the same
     version/epoch/capture invalidation protocol as the transformer cast
     caches. Replaces the per-call chain of ~26 cast/cat/transpose nodes."""
-    from ._ext import load_ext
-    from .transformer import CAPTURE_REFRESH, _weights_epoch
-
     ext = load_ext(required=True)
-    key = (
-        linear.weight._version, gru.weight_ih._version, gru.weight_hh._version,
-        linear.bias._version, gru.bias_ih._version, gru.bias_hh._version,
-        _weights_epoch[0],
-    )
-    cache = getattr(gru, "_dfa_pack_cache", None)
-    if cache is not None and not CAPTURE_REFRESH[0] and cache[0] == key:
-        return cache[1]
+    srcs = (linear.weight, linear.bias, gru.weight_ih, gru.weight_hh,
+            gru.bias_ih, gru.bias_hh)
     H = gru.weight_hh.shape[1]
-    dev = gru.weight_hh.device
-    bf = torch.bfloat16
-    if cache is None:
-        buf = {
-            "w_e16": torch.empty(H, H, dtype=bf, device=dev),
-            "b_e16": torch.empty(H, dtype=bf, device=dev),
-            "Wcat": torch.empty(4 * H, 2 * H, dtype=bf, device=dev),
-            "WcatT": torch.empty(2 * H, 4 * H, dtype=bf, device=dev),
-            "b_cat": torch.empty(4 * H, dtype=bf, device=dev),
-            "W_eT": torch.empty(H, H, dtype=bf, device=dev),
-            "Wcat_perm": torch.empty(4 * H, 2 * H, dtype=bf, device=dev),
-            "b_perm": torch.empty(4 * H, dtype=bf, device=dev),
+
+    def alloc():
+        shapes = {
+            "w_e16": (H, H), "b_e16": (H,), "Wcat": (4 * H, 2 * H),
+            "WcatT": (2 * H, 4 * H), "b_cat": (4 * H,), "W_eT": (H, H),
+            "Wcat_perm": (4 * H, 2 * H), "b_perm": (4 * H,),
         }
-    else:
-        buf = cache[1]
-    ext.pack_gru_weights(
-        linear.weight.detach(), linear.bias.detach(), gru.weight_ih.detach(),
-        gru.weight_hh.detach(), gru.bias_ih.detach(), gru.bias_hh.detach(),
-        buf["w_e16"], buf["b_e16"], buf["Wcat"], buf["WcatT"], buf["b_cat"],
-        buf["W_eT"], buf["Wcat_perm"], buf["b_perm"],
-    )
-    gru._dfa_pack_cache = (key, buf)
-    return buf
+        return {k: torch.empty(shp, dtype=torch.bfloat16, device=gru.weight_hh.device)
+                for k, shp in shapes.items()}
+
+    def fill(buf):
+        ext.pack_gru_weights(
+            *(p.detach() for p in srcs),
+            buf["w_e16"], buf["b_e16"], buf["Wcat"], buf["WcatT"], buf["b_cat"],
+            buf["W_eT"], buf["Wcat_perm"], buf["b_perm"],
+        )
+
+    return derived(gru, "_dfa_pack_cache", srcs, alloc, fill)
 
 
 class _GGNNFused(torch.autograd.Function):
@@ -241,8 +223,6 @@ class _GGNNFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_e, b_e, w_ih, w_hh, b_ih, b_hh, buf, graph, n_steps):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         h_final, HH, M, R, Z, Nn, HN = ext.ggnn_fused_fwd(
             graph.indptr, graph.indices, x, buf["w_e16"], buf["b_e16"],
@@ -258,14 +238,10 @@ class _GGNNFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         x, W_eT, WcatT, HH, M, R, Z, Nn, HN, t_indptr, t_indices = ctx.saved_tensors
         params = ctx.we_refs
-        direct = all(getattr(q, "_dfa_w16", None) is not None and q.grad is not None
-                     for q in params)
-        if direct:
+        if direct_grads(*params):
             w_e, b_e, w_ih, w_hh, b_ih, b_hh = params
             grad_x, *_ = ext.ggnn_fused_bwd(
                 grad_out.contiguous(), t_indptr, t_indices, x, W_eT, WcatT,
@@ -333,7 +309,6 @@ def attn_pool(x: torch.Tensor, gate_logits: torch.Tensor, graph) -> torch.Tensor
 
 def segment_max(values: torch.Tensor, graph) -> torch.Tensor:
     """K7 label reduction (no grad)."""
-    ext = ext_for(values) if values.is_floating_point() or values.is_cuda else None
     if values.is_cuda:
         ext = ext_for(values)
         return ext.segment_max(values.contiguous(), graph.node_offsets)
@@ -348,8 +323,6 @@ class _GatePool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, wg, bg, node_offsets):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         x1c, x2c = x1.contiguous(), x2.contiguous()
         out, alpha, pooled32, gid = ext.gate_pool_fwd(
@@ -361,13 +334,10 @@ class _GatePool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         x1, x2, wg, alpha, node_offsets, pooled32, gid = ctx.saved_tensors
         wgp, bgp = ctx.gparams
-        if (getattr(wgp, "_dfa_w16", None) is not None and wgp.grad is not None
-                and bgp is not None and bgp.grad is not None):
+        if direct_grads(wgp, bgp):
             gx1, gx2, _, _ = ext.gate_pool_bwd(
                 grad_out.contiguous(), x1, x2, wg.detach().reshape(-1).contiguous(),
                 alpha, node_offsets, pooled32, gid, out_wg=wgp.grad, out_bg=bgp.grad,
@@ -393,8 +363,6 @@ class _MLP3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w3, b3):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         xc = x.contiguous()
         logits, h1, h2 = ext.mlp3_fwd(
@@ -408,13 +376,10 @@ class _MLP3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         x, h1, h2, w1, w2, w3 = ctx.saved_tensors
         ps = ctx.mparams
-        if all(getattr(q, "_dfa_w16", None) is not None and q.grad is not None
-               for q in ps):
+        if direct_grads(*ps):
             (dx,) = ext.mlp3_bwd(
                 dlogits.float().contiguous(), x, h1, h2, w1.detach().contiguous(),
                 w2.detach().contiguous(), w3.detach().reshape(-1).contiguous(),
@@ -442,41 +407,33 @@ def _node_head_cache(lin1: torch.nn.Linear, lin2: torch.nn.Linear):
     transposes for the backward's dgrad products. Refreshed IN PLACE while
     CAPTURE_REFRESH is set so a captured step's replays re-derive them
     from the updated master weights."""
-    from .transformer import CAPTURE_REFRESH, _shadow_w16, _weights_epoch
+    w1, w2 = lin1.weight, lin2.weight
+    s1, s2 = _shadow_w16(w1), _shadow_w16(w2)
 
-    s1, s2 = _shadow_w16(lin1.weight), _shadow_w16(lin2.weight)
-    key = (lin1.weight._version, lin2.weight._version, _weights_epoch[0],
-           s1 is not None, s2 is not None)
-    cache = getattr(lin1, "_dfa_nh_cache", None)
-    if cache is not None and cache[1]["w1t"].device != lin1.weight.device:
-        cache = None  # module moved after caching
-    if cache is not None and not CAPTURE_REFRESH[0] and cache[0] == key:
-        buf = cache[1]
-        return (s1 if s1 is not None else buf["w1"],
-                s2 if s2 is not None else buf["w2"], buf["w1t"], buf["w2t"])
-    bf = torch.bfloat16
-    if cache is None or cache[0][3:] != key[3:]:
-        dev = lin1.weight.device
+    def alloc():
+        bf, dev = torch.bfloat16, w1.device
         buf = {
-            "w1t": torch.empty(lin1.weight.shape[::-1], dtype=bf, device=dev),
-            "w2t": torch.empty(lin2.weight.shape[::-1], dtype=bf, device=dev),
+            "w1t": torch.empty(w1.shape[::-1], dtype=bf, device=dev),
+            "w2t": torch.empty(w2.shape[::-1], dtype=bf, device=dev),
         }
         if s1 is None:
-            buf["w1"] = torch.empty(lin1.weight.shape, dtype=bf, device=dev)
+            buf["w1"] = torch.empty(w1.shape, dtype=bf, device=dev)
         if s2 is None:
-            buf["w2"] = torch.empty(lin2.weight.shape, dtype=bf, device=dev)
-    else:
-        buf = cache[1]
-    if s1 is None:
-        buf["w1"].copy_(lin1.weight.detach())
-    if s2 is None:
-        buf["w2"].copy_(lin2.weight.detach())
-    w1 = s1 if s1 is not None else buf["w1"]
-    w2 = s2 if s2 is not None else buf["w2"]
-    buf["w1t"].copy_(w1.t())
-    buf["w2t"].copy_(w2.t())
-    lin1._dfa_nh_cache = (key, buf)
-    return w1, w2, buf["w1t"], buf["w2t"]
+            buf["w2"] = torch.empty(w2.shape, dtype=bf, device=dev)
+        return buf
+
+    def fill(buf):
+        if s1 is None:
+            buf["w1"].copy_(w1.detach())
+        if s2 is None:
+            buf["w2"].copy_(w2.detach())
+        buf["w1t"].copy_((s1 if s1 is not None else buf["w1"]).t())
+        buf["w2t"].copy_((s2 if s2 is not None else buf["w2"]).t())
+
+    buf = derived(lin1, "_dfa_nh_cache", (w1, w2), alloc, fill,
+                  extra=(s1 is not None, s2 is not None))
+    return (s1 if s1 is not None else buf["w1"],
+            s2 if s2 is not None else buf["w2"], buf["w1t"], buf["w2t"])
 
 
 class _NodeHead(torch.autograd.Function):
@@ -495,9 +452,6 @@ class _NodeHead(torch.autograd.Function):
             logits, x, h1, h2 = ref.node_head_fwd(h, fe, w1, b1, w2, b2, w3, b3)
             ctx.save_for_backward(x, h1, h2, w1, w2, w3)
             return logits
-        from ._ext import load_ext
-        from .transformer import _bias_f32
-
         ext = load_ext(required=True)
         w1_16, w2_16, w1t, w2t = w16
         w3f = _bias_f32(w3).reshape(-1)
@@ -518,14 +472,10 @@ class _NodeHead(torch.autograd.Function):
             x, h1, h2, w1, w2, w3 = ctx.saved_tensors
             grads = ref.node_head_bwd(dlogits, x, h1, h2, w1, w2, w3, ctx.d1)
             return (*grads, None)
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         x, h1, h2, w1t, w2t, w3f = ctx.saved_tensors
         dl = dlogits.float().contiguous()
-        direct = all(getattr(q, "_dfa_w16", None) is not None and q.grad is not None
-                     for q in ps)
-        if direct:
+        if direct_grads(*ps):
             # every parameter grad accumulates in-kernel into the flat
             # .grad views (atomic epilogues; a live .grad may already hold
             # an earlier micro-batch's contribution)
@@ -561,8 +511,6 @@ class _BCELogits(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, weight, pos_weight):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         l32 = logits.float().contiguous()
         y32 = labels.float().contiguous()
@@ -576,8 +524,6 @@ class _BCELogits(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        from ._ext import load_ext
-
         ext = load_ext(required=True)
         l32, y32, out2 = ctx.saved_tensors
         dlogits = ext.bce_logits_bwd(l32, y32, ctx.w32, ctx.pw,

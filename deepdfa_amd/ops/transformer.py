@@ -12,6 +12,9 @@ from typing import Optional
 import torch
 
 from ._ext import load_ext
+from ._weights import (  # noqa: F401  (the first five are re-exported)
+    CAPTURE_REFRESH, _bias_f32, _shadow_w16, _weights_epoch, bump_weights_epoch,
+    derived, direct_grads, packed_grad, packed_shadow)
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -66,46 +69,6 @@ def bias_gelu(x, bias):
     if x.is_cuda:
         return _BiasGelu.apply(x, bias)
     return torch.nn.functional.gelu(x.float() + bias.float()).to(x.dtype)
-
-
-# cast-cache invalidation epoch: optimizers that write master weights
-# through raw extension kernels (FlatAdamW) bypass torch's version
-# counters, so they bump this instead
-_weights_epoch = [0]
-
-# hipGraph capture mode: when True, fused_linear re-casts weights INTO its
-# cached buffers every call so the cast is captured and replays against the
-# updated master weights
-CAPTURE_REFRESH = [False]
-
-
-def bump_weights_epoch():
-    _weights_epoch[0] += 1
-
-
-def _shadow_w16(weight):
-    """The optimizer-maintained flat bf16 shadow view of `weight`
-    (parallel/optim.py FlatAdamW), re-synced if a torch-level write
-    (checkpoint load, broadcast) moved the parameter's version counter
-    since the last sync. None when no flat optimizer owns the weight."""
-    w16 = getattr(weight, "_dfa_w16", None)
-    if w16 is None:
-        return None
-    if weight._version != weight._dfa_w16_ver:
-        w16.copy_(weight.detach())
-        weight._dfa_w16_ver = weight._version
-    return w16
-
-
-def _bias_f32(bias):
-    """Master-fp32 biases are used in place (no copy); anything else is
-    cast-copied (rare: only models trained without the flat optimizer)."""
-    if bias is None:
-        return None
-    b = bias.detach()
-    if b.dtype == torch.float32 and b.is_contiguous():
-        return b
-    return b.float().contiguous()
 
 
 _seed_state = {"base": None, "ctr": 0}
@@ -183,57 +146,41 @@ class _LinearBf16(torch.autograd.Function):
         # fat shapes route to the library GEMMs and never read wt16 (backward
         # uses w16 directly), so the transpose copy is skipped for them
         fat = weight.shape[0] > 1024 or weight.shape[1] > 1024
+        bf = torch.bfloat16
         w16 = _shadow_w16(weight)
         if w16 is not None:
             # optimizer-maintained bf16 shadow (parallel/optim.py): no cast
             # kernel — the adamw kernel wrote this view at the last step.
             # Only the transposed copy (square shapes) needs per-step refresh.
             b32 = _bias_f32(bias)
-            if fat:
-                wt16 = None
-            else:
-                cache = getattr(weight, "_dfa_wt_cache", None)
-                key = (weight._version, _weights_epoch[0])
-                if cache is None:
-                    wt16 = w16.t().contiguous()
-                    weight._dfa_wt_cache = (key, wt16)
-                elif CAPTURE_REFRESH[0] or cache[0] != key:
-                    _, wt16 = cache
-                    wt16.copy_(w16.t())
-                    weight._dfa_wt_cache = (key, wt16)
-                else:
-                    _, wt16 = cache
+            wt16 = None if fat else derived(
+                weight, "_dfa_wt_cache", (weight,),
+                lambda: torch.empty(weight.shape[::-1], dtype=bf, device=weight.device),
+                lambda wt: wt.copy_(w16.t()))
         else:
-            # no flat optimizer: cache the bf16 / transposed weight per
-            # parameter VERSION — the cast and transpose copies otherwise
-            # dominate the elementwise kernel count (~3 x 72 linears/step)
-            cache = getattr(weight, "_dfa_cast_cache", None)
-            key = (weight._version, _weights_epoch[0])
-            if cache is None:
-                w16 = weight.detach().to(torch.bfloat16).contiguous()
-                wt16 = None if fat else w16.t().contiguous()
-                b32 = bias.detach().float().contiguous() if bias is not None else None
-                weight._dfa_cast_cache = (key, w16, wt16, b32)
-            elif CAPTURE_REFRESH[0] or cache[0] != key:
-                # refresh INTO the cached buffers: under hipGraph capture the
-                # cast must be part of the graph (stable addresses, re-run
-                # each replay); in eager it re-casts only when the key moved
-                _, w16, wt16, b32 = cache
+            # no flat optimizer: cache the bf16 / transposed weight and the
+            # fp32 bias per parameter VERSION — the cast and transpose copies
+            # otherwise dominate the elementwise kernel count (~3 x 72
+            # linears/step)
+            def alloc():
+                dev = weight.device
+                return (
+                    torch.empty(weight.shape, dtype=bf, device=dev),
+                    None if fat else torch.empty(weight.shape[::-1], dtype=bf, device=dev),
+                    None if bias is None else torch.empty(
+                        bias.shape, dtype=torch.float32, device=dev),
+                )
+
+            def fill(bufs):
+                w16, wt16, b32 = bufs
                 w16.copy_(weight.detach())
                 if wt16 is not None:
                     wt16.copy_(w16.t())
-                if bias is not None:
-                    if b32 is None:
-                        b32 = bias.detach().float().contiguous()
-                    else:
-                        b32.copy_(bias.detach())
-                weight._dfa_cast_cache = (key, w16, wt16, b32)
-            else:
-                _, w16, wt16, b32 = cache
-                if bias is not None and b32 is None:
-                    b32 = bias.detach().float().contiguous()
-        if bias is None:
-            b32 = None
+                if b32 is not None:
+                    b32.copy_(bias.detach())
+
+            w16, wt16, b32 = derived(weight, "_dfa_cast_cache", (weight, bias),
+                                     alloc, fill, extra=(bias is not None,))
         # shape dispatch (measured, profiles/optimization_r2.md): our gemm2
         # beats hipBLASLt on the square 768-ish shapes; the library wins the
         # fat no-bias ones (K or COL >= ~2k)
@@ -262,12 +209,12 @@ class _LinearBf16(torch.autograd.Function):
         dw = db = None
         wp, bp = ctx.wp, ctx.bp
         if ctx.needs_input_grad[1]:
-            if getattr(wp, "_dfa_w16", None) is not None and wp.grad is not None:
+            if direct_grads(wp):
                 ext.wgrad(dy2d, x2d, out=wp.grad)
             else:
                 dw = ext.wgrad(dy2d, x2d)  # (COL, K) fp32
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            if getattr(bp, "_dfa_w16", None) is not None and bp.grad is not None:
+            if direct_grads(bp):
                 ext.colsum(dy2d, out=bp.grad)
             else:
                 db = ext.colsum(dy2d)
@@ -361,8 +308,7 @@ class _RMSNorm(torch.autograd.Function):
         dy = dy.contiguous()
         dx = ext.rmsnorm_bwd(dy, x, wf, rstd)
         wp = ctx.wp
-        if (getattr(wp, "_dfa_w16", None) is not None and wp.grad is not None
-                and ctx.needs_input_grad[1]):
+        if direct_grads(wp) and ctx.needs_input_grad[1]:
             # direct accumulation into the flat .grad view (parallel/optim.py)
             ext.rmsnorm_wgrad(dy, x, rstd, out=wp.grad)
             return dx, None, None
@@ -404,8 +350,7 @@ class _EmbeddingLookup(torch.autograd.Function):
         ext = load_ext(required=True)
         (indices,) = ctx.saved_tensors
         wp = ctx.wp
-        if (getattr(wp, "_dfa_w16", None) is not None and wp.grad is not None
-                and ctx.w_dtype == torch.float32):
+        if direct_grads(wp) and ctx.w_dtype == torch.float32:
             # scatter straight into the flat fp32 .grad view (pre-zeroed):
             # skips a (V, D) zeros + full-table AccumulateGrad add
             ext.embed_scatter(dy.contiguous(), indices.reshape(-1).contiguous(),
@@ -468,6 +413,27 @@ def layer_norm_res_dropout(h, res, weight, bias, dropout_p=0.0, eps=1e-5):
     )
 
 
+def _packed_cast(slot, ws, bs=()):
+    """(w16, b32): the bf16 row-stack of the (D, K) weights `ws` and the fp32
+    stack of the biases `bs` (None without biases), for parameters the flat
+    optimizer does not hold back-to-back. Cached on ws[0] under `slot`;
+    refreshed by one slice copy per parameter."""
+    D, dev = ws[0].shape[0], ws[0].device
+
+    def alloc():
+        return (
+            torch.empty(len(ws) * D, ws[0].shape[1], dtype=torch.bfloat16, device=dev),
+            torch.empty(len(bs) * D, dtype=torch.float32, device=dev) if bs else None,
+        )
+
+    def fill(bufs):
+        for buf, ps in zip(bufs, (ws, bs)):
+            for i, p in enumerate(ps):
+                buf[i * D:(i + 1) * D].copy_(p.detach())
+
+    return derived(ws[0], slot, (*ws, *bs), alloc, fill, extra=(len(bs),))
+
+
 class _QKVLinear(torch.autograd.Function):
     """Fused QKV projection: one (N, 3D) gemm2 / wgrad per layer instead of
     three 768-column calls (a 64x6-block grid underfills 256 CUs; the
@@ -478,49 +444,23 @@ class _QKVLinear(torch.autograd.Function):
         ext = load_ext(required=True)
         x2d = x.reshape(-1, x.shape[-1]).contiguous()
         has_bias = bq is not None
-        # bias-free q/k/v defined back-to-back (T5) sit ADJACENT in the flat
-        # optimizer's bf16 shadow: the packed (3D, K) weight is a zero-copy
-        # view of the shadow buffer — no per-step packing or cast kernels
-        sq, sk, sv = _shadow_w16(wq), _shadow_w16(wk), _shadow_w16(wv)
-        if (
-            sq is not None and sk is not None and sv is not None
-            and sk.data_ptr() == sq.data_ptr() + 2 * sq.numel()
-            and sv.data_ptr() == sk.data_ptr() + 2 * sk.numel()
-        ):
-            base, off = wq._dfa_w16_base, wq._dfa_w16_off
-            n3 = sq.numel() + sk.numel() + sv.numel()
-            w16 = base[off : off + n3].view(3 * wq.shape[0], wq.shape[1])
-            b32 = None
-            if has_bias:
-                cache = getattr(wq, "_dfa_qkv_cache", None)
-                key = (bq._version, bk._version, bv._version, _weights_epoch[0])
-                if cache is None or CAPTURE_REFRESH[0] or cache[0] != key:
-                    b32 = torch.cat([bq.detach(), bk.detach(), bv.detach()]).float()
-                    wq._dfa_qkv_cache = (key, b32)
-                else:
-                    b32 = cache[1]
+        D = wq.shape[0]
+        # q/k/v defined back-to-back sit ADJACENT in the flat optimizer's
+        # bf16 shadow: the packed (3D, K) weight is a zero-copy view of the
+        # shadow buffer — no per-step packing or cast kernels
+        flat = packed_shadow((wq, wk, wv))
+        if flat is not None:
+            w16 = flat.view(3 * D, wq.shape[1])
+            # the biases are fp32 masters already: one cat into the cached
+            # buffer packs them
+            b32 = derived(
+                wq, "_dfa_qkv_bias_cache", (bq, bk, bv),
+                lambda: torch.empty(3 * D, dtype=torch.float32, device=wq.device),
+                lambda b: torch.cat([bq.detach(), bk.detach(), bv.detach()], out=b),
+            ) if has_bias else None
         else:
-            cache = getattr(wq, "_dfa_qkv_cache", None)
-            key = (wq._version, wk._version, wv._version, _weights_epoch[0])
-            if cache is None:
-                wcat = torch.cat([wq.detach(), wk.detach(), wv.detach()])
-                w16 = wcat.to(torch.bfloat16).contiguous()
-                b32 = (torch.cat([bq.detach(), bk.detach(), bv.detach()]).float().contiguous()
-                       if has_bias else None)
-                wq._dfa_qkv_cache = (key, w16, b32)
-            elif CAPTURE_REFRESH[0] or cache[0] != key:
-                _, w16, b32 = cache
-                D = wq.shape[0]
-                w16[:D].copy_(wq.detach())
-                w16[D:2 * D].copy_(wk.detach())
-                w16[2 * D:].copy_(wv.detach())
-                if has_bias:
-                    b32[:D].copy_(bq.detach())
-                    b32[D:2 * D].copy_(bk.detach())
-                    b32[2 * D:].copy_(bv.detach())
-                wq._dfa_qkv_cache = (key, w16, b32)
-            else:
-                _, w16, b32 = cache
+            w16, b32 = _packed_cast("_dfa_qkv_cache", (wq, wk, wv),
+                                    (bq, bk, bv) if has_bias else ())
         out = ext.gemm2(x2d, w16, b32, None)
         ctx.save_for_backward(x2d, w16)
         ctx.has_bias = has_bias
@@ -539,16 +479,9 @@ class _QKVLinear(torch.autograd.Function):
         # q/k/v grads adjacent in the flat grad buffer (T5, bias-free):
         # ONE wgrad accumulates the packed (3D, K) grad straight into the
         # flat .grad region — no zeros, no slicing, no AccumulateGrad adds
-        if (
-            not ctx.has_bias
-            and getattr(wq, "_dfa_w16", None) is not None and wq.grad is not None
-            and wk.grad is not None and wv.grad is not None
-            and wk.grad.data_ptr() == wq.grad.data_ptr() + 4 * wq.numel()
-            and wv.grad.data_ptr() == wk.grad.data_ptr() + 4 * wk.numel()
-        ):
-            n3 = wq.numel() + wk.numel() + wv.numel()
-            g3 = wq._dfa_gbase[wq._dfa_goff : wq._dfa_goff + n3].view(3 * D, -1)
-            ext.wgrad(dy2d, x2d, out=g3)
+        g3 = None if ctx.has_bias else packed_grad((wq, wk, wv))
+        if g3 is not None:
+            ext.wgrad(dy2d, x2d, out=g3.view(3 * D, -1))
             return (dx.view(ctx.x_shape), None, None, None, None, None, None)
         dw = ext.wgrad(dy2d, x2d)  # (3D, K) fp32
         if ctx.has_bias:
@@ -578,28 +511,11 @@ class _KVLinear(torch.autograd.Function):
     def forward(ctx, x, wk, wv):
         ext = load_ext(required=True)
         x2d = x.reshape(-1, x.shape[-1]).contiguous()
-        sk, sv = _shadow_w16(wk), _shadow_w16(wv)
-        if (
-            sk is not None and sv is not None
-            and sv.data_ptr() == sk.data_ptr() + 2 * sk.numel()
-        ):
-            base, off = wk._dfa_w16_base, wk._dfa_w16_off
-            n2 = sk.numel() + sv.numel()
-            w16 = base[off : off + n2].view(2 * wk.shape[0], wk.shape[1])
+        flat = packed_shadow((wk, wv))
+        if flat is not None:
+            w16 = flat.view(2 * wk.shape[0], wk.shape[1])
         else:
-            cache = getattr(wk, "_dfa_kv_cache", None)
-            key = (wk._version, wv._version, _weights_epoch[0])
-            if cache is None:
-                w16 = torch.cat([wk.detach(), wv.detach()]).to(torch.bfloat16).contiguous()
-                wk._dfa_kv_cache = (key, w16)
-            elif CAPTURE_REFRESH[0] or cache[0] != key:
-                _, w16 = cache
-                D = wk.shape[0]
-                w16[:D].copy_(wk.detach())
-                w16[D:].copy_(wv.detach())
-                wk._dfa_kv_cache = (key, w16)
-            else:
-                _, w16 = cache
+            w16, _ = _packed_cast("_dfa_kv_cache", (wk, wv))
         out = ext.gemm2(x2d, w16, None, None)
         ctx.save_for_backward(x2d, w16)
         ctx.x_shape = x.shape
@@ -614,14 +530,9 @@ class _KVLinear(torch.autograd.Function):
         dx = torch.matmul(dy2d, w16)  # (N, 2D) @ (2D, D): fat K, library wins
         D = w16.shape[0] // 2
         wk, wv = ctx.wparams
-        if (
-            getattr(wk, "_dfa_w16", None) is not None and wk.grad is not None
-            and wv.grad is not None
-            and wv.grad.data_ptr() == wk.grad.data_ptr() + 4 * wk.numel()
-        ):
-            n2 = wk.numel() + wv.numel()
-            g2 = wk._dfa_gbase[wk._dfa_goff : wk._dfa_goff + n2].view(2 * D, -1)
-            ext.wgrad(dy2d, x2d, out=g2)
+        g2 = packed_grad((wk, wv))
+        if g2 is not None:
+            ext.wgrad(dy2d, x2d, out=g2.view(2 * D, -1))
             return dx.view(ctx.x_shape), None, None
         dw = ext.wgrad(dy2d, x2d)
         return dx.view(ctx.x_shape), dw[:D], dw[D:]
@@ -761,24 +672,17 @@ class _LMHeadCE(torch.autograd.Function):
         h2d = h.reshape(-1, K).to(torch.bfloat16).contiguous()
         V = weight.shape[0]
         Vp = (V + 127) // 128 * 128
-        # padded bf16 vocab-weight cache (same invalidation protocol as
-        # _LinearBf16: parameter version + weights epoch + capture refresh)
-        cache = getattr(weight, "_dfa_vocab_cache", None)
-        key = (weight._version, _weights_epoch[0])
-        if cache is None:
-            Wp = torch.zeros(Vp, K, dtype=torch.bfloat16, device=weight.device)
+
+        def fill(Wp):  # padded bf16 vocab weight: rows >= V stay zero
+            # from the optimizer's bf16 shadow when present: a bf16->bf16
+            # copy is 2/3 the traffic of the fp32 cast at V=32100
             src = _shadow_w16(weight)
             Wp[:V].copy_(src if src is not None else weight.detach())
-            weight._dfa_vocab_cache = (key, Wp)
-        elif CAPTURE_REFRESH[0] or cache[0] != key:
-            _, Wp = cache
-            # refresh from the optimizer's bf16 shadow when present: a
-            # bf16->bf16 copy is 2/3 the traffic of the fp32 cast at V=32100
-            src = _shadow_w16(weight)
-            Wp[:V].copy_(src if src is not None else weight.detach())
-            weight._dfa_vocab_cache = (key, Wp)
-        else:
-            _, Wp = cache
+
+        Wp = derived(
+            weight, "_dfa_vocab_cache", (weight,),
+            lambda: torch.zeros(Vp, K, dtype=torch.bfloat16, device=weight.device),
+            fill)
         tgt = targets.reshape(-1).to(torch.int32)
         tgt = torch.where(tgt == -100, tgt.new_full((), -1), tgt).contiguous()
         loss_rows, lse = ext.lmhead_ce_fwd(h2d, Wp, tgt, float(scale), V)
