@@ -195,6 +195,16 @@ __global__ __launch_bounds__(NW * 64, 12 / NW) void flash_fwd_kernel(
 #define V_BUF(i) (v_lds + (i) * (TK * 128 + FWD_VBYTES))
   uint4v kreg[NPASS], vreg[NPASS];
   int cur = 0;
+  // this lane's two query columns. With L % 128 == 64 the last query block
+  // has waves that lie wholly past L (qw and L are multiples of TQW); their
+  // scores are masked below, but bias[.. + qcol] would be read up to 63
+  // columns past the (H, L, L) allocation. Clamp the wave's column window to
+  // [L - TQW, L - 1] instead: qshift is wave-uniform, so it folds into the
+  // scalar base pointer and the key loop gains neither an instruction nor a
+  // VGPR (a per-lane min(qcol, L - 1) cost two, and 0.25 % of a T5 step).
+  const int qcol[2] = {qw + (lane & 15), qw + 16 + (lane & 15)};
+  const int qshift = (qw < L) ? 0 : qw + TQW - L;
+  const float* bias_h = bias ? bias + (long)h * L * L - qshift : nullptr;
   if (kv_end > 0) {
     load_tile(0, kreg, vreg);
     write_tile(K_BUF(0), V_BUF(0), kreg, vreg);
@@ -235,7 +245,6 @@ __global__ __launch_bounds__(NW * 64, 12 / NW) void flash_fwd_kernel(
     // scores -> probabilities transform IN s_acc: a separate p[4][2][4]
     // copy cost 32 VGPRs (232 total = 2 waves/SIMD; the kernel is
     // latency-bound at that occupancy, PMC WAIT_ANY 35%)
-    const int qcol[2] = {qw + (lane & 15), qw + 16 + (lane & 15)};
     float tile_max[2] = {-3.4e38f, -3.4e38f};
 #pragma unroll
     for (int fk = 0; fk < 4; ++fk)
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(NW * 64, 12 / NW) void flash_fwd_kernel(
         // one unrolled load hit one 64-B line (row-major (H, q, key) made
         // every lane fetch its own line: measured ~half the biased
         // kernel's time, tools/flash_bias_probe.py)
-        if (bias) s += bias[((long)h * L + key) * L + qcol[fq]];
+        if (bias) s += bias_h[(long)key * L + qcol[fq]];
           const bool masked = key >= vl || (causal && key > qcol[fq]) || qcol[fq] >= L;
           s = masked ? -3.4e38f : s;
           s_acc[fk][fq][i] = s;
@@ -457,6 +466,9 @@ __device__ __forceinline__ void recompute_pT(
     const char* k_lds, const bf16x8 q_frag[2][2], const float* __restrict__ bias,
     const float lse_w[2], int lane, int h, int L, int qw, int kv0,
     int vl, float scale, int causal, float p[4][2][4]) {
+  // a wave wholly past L (partial last q block, masked below) reads the
+  // bias through a column window clamped to [L - TQW, L - 1]: see the forward
+  const int qshift = (qw < L) ? 0 : qw + TQW - L;
   f32x4 s_acc[4][2] = {};
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
@@ -483,7 +495,7 @@ __device__ __forceinline__ void recompute_pT(
       for (int i = 0; i < 4; ++i) {
         const int key = kv0 + fk * 16 + (lane >> 4) * 4 + i;
         float s = s_acc[fk][fq][i] * scale;
-        if (bias) s += bias[((long)h * L + key) * L + qcol];  // (H, key, qcol) layout
+        if (bias) s += bias[((long)h * L + key) * L + qcol - qshift];  // (H, key, qcol) layout
         const bool masked = key >= vl || (causal && key > qcol) || qcol >= L;
         p[fk][fq][i] = masked ? 0.f : __expf(s - lse_w[fq]);
       }
