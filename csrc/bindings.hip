@@ -920,20 +920,31 @@ void launch_lmhead_ce_bwd(const __hip_bfloat16*, const __hip_bfloat16*, const in
                           const float*, const float*, float, long, int, int, int,
                           __hip_bfloat16*, hipStream_t);
 
+// the operands both lmhead_ce kernels read: h (M,K) bf16, Wp (Vp,K) bf16,
+// targets (M,) int32; the kernels index all three without bounds checks
+static void check_lmhead_ce(const at::Tensor& h, const at::Tensor& Wp,
+                            const at::Tensor& targets, int64_t V) {
+  CHECK_GPU(h);
+  CHECK_GPU(Wp);
+  CHECK_GPU(targets);
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && Wp.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(targets.scalar_type() == at::kInt && targets.is_contiguous());
+  TORCH_CHECK(h.dim() == 2 && Wp.dim() == 2);
+  const long M = h.size(0), K = h.size(1), Vp = Wp.size(0);
+  TORCH_CHECK(Wp.size(1) == K && M % 128 == 0 && K % 64 == 0 && Vp % 128 == 0,
+              "lmhead_ce geometry violated: ", M, "x", K, " vocab ", Vp);
+  TORCH_CHECK(V > 0 && V <= Vp, "lmhead_ce: V = ", V, " outside (0, Vp = ", Vp, "]");
+  TORCH_CHECK(targets.numel() == M);
+}
+
 // K21 forward: per-row (loss, lse) of CE(softmax(scale * h @ Wp^T), target)
 // without materializing logits. h (M,K) bf16, Wp (Vp,K) bf16 zero-padded
 // past V, targets (M,) int32 with -1 = ignore. csrc/lmhead_ce.hip.
 std::vector<at::Tensor> lmhead_ce_fwd(at::Tensor h, at::Tensor Wp, at::Tensor targets,
                                       double scale, int64_t V) {
-  CHECK_GPU(h);
-  CHECK_GPU(Wp);
-  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && Wp.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(targets.scalar_type() == at::kInt && targets.is_contiguous());
+  check_lmhead_ce(h, Wp, targets, V);
   const long M = h.size(0);
   const int K = h.size(1), Vp = Wp.size(0);
-  TORCH_CHECK(Wp.size(1) == K && M % 128 == 0 && K % 64 == 0 && Vp % 128 == 0,
-              "lmhead_ce geometry violated: ", M, "x", K, " vocab ", Vp);
-  TORCH_CHECK(targets.numel() == M);
   const int n_chunks = (Vp / 128 + 7) / 8;
   auto fopt = h.options().dtype(at::kFloat);
   auto pmax = at::empty({M, n_chunks}, fopt);
@@ -953,7 +964,9 @@ std::vector<at::Tensor> lmhead_ce_fwd(at::Tensor h, at::Tensor Wp, at::Tensor ta
 // recomputed tile-by-tile (cols >= V zeroed).
 at::Tensor lmhead_ce_bwd(at::Tensor h, at::Tensor Wp, at::Tensor targets,
                          at::Tensor lse, at::Tensor gscale, double scale, int64_t V) {
-  CHECK_GPU(h);
+  check_lmhead_ce(h, Wp, targets, V);
+  CHECK_GPU(lse);
+  CHECK_GPU(gscale);
   const long M = h.size(0);
   const int K = h.size(1), Vp = Wp.size(0);
   TORCH_CHECK(lse.scalar_type() == at::kFloat && gscale.scalar_type() == at::kFloat);

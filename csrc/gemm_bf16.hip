@@ -12,41 +12,11 @@
 // N % 128 == 0, K % 64 == 0, COL % 128 == 0.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-#define WAVE 64
+#include "mfma_tile.h"
+
 #define BM2 128
-#define BN2 128
-#define BK2 64
-#define ROWB2 128  // bytes per LDS row (64 bf16)
-
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ int g2_swz(int row, int byte) {
-  return row * ROWB2 + (byte ^ ((row & 7) << 4));
-}
-
-// stage one 128x64 bf16 tile into LDS via glds: 16 KiB = 16 pieces of 1 KiB,
-// 4 pieces per wave. Lane l of piece c covers (row = 8c + l/8,
-// kbyte = (l%8)*16); the source byte offset carries the XOR swizzle.
-template <int NP>  // 1-KiB pieces per wave: 4 for 128-row tiles, 2 for 64
-__device__ __forceinline__ void g2_stage(const bf16* __restrict__ src_base,
-                                         long row_stride_elems, int kk,
-                                         char* lds, int wid, int lane) {
-#pragma unroll
-  for (int c4 = 0; c4 < NP; ++c4) {
-    const int c = wid * NP + c4;
-    const int row = 8 * c + (lane >> 3);
-    const int kbyte = (lane & 7) * 16;
-    const int src_byte = kbyte ^ ((row & 7) << 4);
-    const bf16* gsrc = src_base + row * row_stride_elems + kk + src_byte / 2;
-    __builtin_amdgcn_global_load_lds(
-        reinterpret_cast<const unsigned int*>(gsrc),
-        reinterpret_cast<unsigned int*>(lds + c * 1024 + (lane & 63) * 16), 16, 0, 0);
-  }
-}
+#define BN2 TILE_BN
 
 // BMT2 = 128 normally; 64 when the 128-row grid would underfill the chip
 // (e.g. the CodeT5 decoder's N=4096 projections: 32x6 = 192 blocks on 512
@@ -57,12 +27,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(
     const float* __restrict__ bias, const bf16* __restrict__ addend,
     bf16* __restrict__ out, int N, int K, int COL) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // double-buffered A and B tiles ((BMT2+128)*128 B each buffer pair)
-  // (pointer arrays with addrspace casts are rejected as static
-  // initializers; compute the buffer base per use)
-#define A_BUF(i) (smem + (i) * (BMT2 * 128 + 16384))
-#define B_BUF(i) (smem + BMT2 * 128 + (i) * (BMT2 * 128 + 16384))
-
+  // double-buffered A and B tiles: tile_lds_bytes(BMT2)
   const int r0 = blockIdx.x * BMT2;
   const int c0 = blockIdx.y * BN2;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -73,46 +38,8 @@ __global__ __launch_bounds__(256) void gemm2_kernel(
   constexpr int MF = BMT2 / 32;  // a-fragments per row-wave
   f32x4 acc[MF][4] = {};
 
-  const int nt = K / BK2;
-  int cur = 0;
-  g2_stage<BMT2 / 32>(A + (long)r0 * K, K, 0, A_BUF(0), wid, lane);
-  g2_stage<4>(W + (long)c0 * K, K, 0, B_BUF(0), wid, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) {
-      g2_stage<BMT2 / 32>(A + (long)r0 * K, K, (t + 1) * BK2, A_BUF(cur ^ 1), wid, lane);
-      g2_stage<4>(W + (long)c0 * K, K, (t + 1) * BK2, B_BUF(cur ^ 1), wid, lane);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int kbyte = ks * 64 + (lane >> 4) * 16;
-      bf16x8 a_frag[MF], b_frag[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        const int brow = wn * 64 + f * 16 + (lane & 15);
-        b_frag[f] = *reinterpret_cast<const bf16x8*>(B_BUF(cur) + g2_swz(brow, kbyte));
-      }
-#pragma unroll
-      for (int f = 0; f < MF; ++f) {
-        const int arow = wm * (BMT2 / 2) + f * 16 + (lane & 15);
-        a_frag[f] = *reinterpret_cast<const bf16x8*>(A_BUF(cur) + g2_swz(arow, kbyte));
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int fm = 0; fm < MF; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < 4; ++fn)
-          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[fm], b_frag[fn], acc[fm][fn], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
+  tile_glds_gemm<BMT2>(acc, smem, A + (long)r0 * K, W + (long)c0 * K, K, lane,
+                       wid);
 
   // epilogue: the D fragment layout (col = lane&15, row = (lane>>4)*4+i)
   // would need 64 x 2-B scalar stores per lane (store-issue bound, T21
@@ -159,13 +86,15 @@ void launch_gemm2(const bf16* A, const bf16* W, const float* bias,
                   const bf16* addend, bf16* out, int N, int K, int COL,
                   hipStream_t stream) {
   const long blocks128 = (long)(N / BM2) * (COL / BN2);
+  // tests/test_gpu_gemm_tiles.py: test_gemm2_64row_tile takes the 64-row
+  // tile, test_gemm2_128row_tile (1024 x 8192 = 512 blocks) the 128-row tile
   if (N % 128 == 0 && blocks128 < 512) {
     const dim3 grid(N / 64, COL / BN2);
-    hipLaunchKernelGGL(gemm2_kernel<64>, grid, dim3(256), 2 * (64 * 128 + 16384),
-                       stream, A, W, bias, addend, out, N, K, COL);
+    hipLaunchKernelGGL(gemm2_kernel<64>, grid, dim3(256),
+                       tile_lds_bytes(64), stream, A, W, bias, addend, out, N, K, COL);
   } else {
     const dim3 grid(N / BM2, COL / BN2);
-    hipLaunchKernelGGL(gemm2_kernel<128>, grid, dim3(256), 65536, stream, A, W,
-                       bias, addend, out, N, K, COL);
+    hipLaunchKernelGGL(gemm2_kernel<128>, grid, dim3(256),
+                       tile_lds_bytes(BM2), stream, A, W, bias, addend, out, N, K, COL);
   }
 }

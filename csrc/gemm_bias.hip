@@ -13,24 +13,12 @@
 // concatenation.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-#define WAVE 64
+#include "mfma_tile.h"
 
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;  // 4 VGPRs
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using uint4v = __attribute__((ext_vector_type(4))) unsigned int;
-
-// tile geometry
+// tile geometry (register-staged pipeline of mfma_tile.h)
 #define BM 64
-#define BN 128
-#define BK 64
-#define ROWB (BK * 2)  // bytes per LDS row (64 bf16)
-
-__device__ __forceinline__ int swz(int row, int byte) {
-  return row * ROWB + (byte ^ ((row & 7) << 4));
-}
+#define BN TILE_BN
 
 // out(N, COL) = concat_K(A1, A2)(N, K) @ W(COL, K)^T + bias
 // grid = (ceil(N/BMT), COL/BN), block = 256 (4 waves, 2x2)
@@ -49,103 +37,17 @@ __global__ __launch_bounds__(256) void gemm_bias_kernel(
     bf16* __restrict__ out, int N, int K,
     int K1, int COL) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;                 // BMT x ROWB
-  char* b_lds = smem + BMT * ROWB;    // BN x ROWB = 16 KiB
 
   const int r0 = blockIdx.x * BMT;
   const int c0 = blockIdx.y * BN;
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
-  const int wid = tid >> 6;           // 4 waves: (wm, wn) = (wid>>1, wid&1)
-  const int wm = wid >> 1;            // 2 row-waves of 32 rows
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;   // 4 waves: (wm, wn) = (wid>>1, wid&1)
+  const int wm = wid >> 1;            // 2 row-waves of BMT/2 rows
   const int wn = wid & 1;             // 2 col-waves of 64 cols
 
   constexpr int MFRAG = BMT / 32;     // fragments per row-wave
   f32x4 acc[MFRAG][4] = {};
-
-  // T14 double-buffered staging: next K-tile's global loads issue before
-  // this tile's MFMAs (these N x 128-ish GEMMs are HBM-latency-bound at
-  // ~1.4 blocks/CU; single-buffered staging serialized load latency with
-  // the MFMA phase)
-  const int srow = tid >> 3;         // 0..31
-  const int soff = (tid & 7) * 16;   // byte offset in row
-  constexpr int NAR = BMT / 32;      // A rows per thread
-  auto load_regs = [&](int kk, uint4v ar[NAR], uint4v br[4]) {
-#pragma unroll
-    for (int p = 0; p < NAR; ++p) {
-      const int rr = srow + p * 32;
-      const int gr = r0 + rr;
-      ar[p] = {};
-      if (gr < N) {
-        const int gk = kk + soff / 2;  // element index in K
-        const bf16* src = (gk < K1) ? (A1 + (long)gr * K1 + gk)
-                                    : (A2 + (long)gr * (K - K1) + (gk - K1));
-        ar[p] = *reinterpret_cast<const uint4v*>(src);
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int rr = srow + p * 32;
-      if constexpr (CT) {
-        br[p] = {};
-        if (c0 + rr >= COL) continue;
-      }
-      br[p] = *reinterpret_cast<const uint4v*>(W + (long)(c0 + rr) * K + kk +
-                                               soff / 2);
-    }
-  };
-  auto write_regs = [&](char* ab, char* bb, const uint4v ar[NAR],
-                        const uint4v br[4]) {
-#pragma unroll
-    for (int p = 0; p < NAR; ++p)
-      *reinterpret_cast<uint4v*>(ab + swz(srow + p * 32, soff)) = ar[p];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      *reinterpret_cast<uint4v*>(bb + swz(srow + p * 32, soff)) = br[p];
-  };
-#define GB_ABUF(i) (a_lds + (i) * (BMT + BN) * ROWB)
-#define GB_BBUF(i) (b_lds + (i) * (BMT + BN) * ROWB)
-  uint4v areg[NAR], breg[4];
-  load_regs(0, areg, breg);
-  write_regs(GB_ABUF(0), GB_BBUF(0), areg, breg);
-  __syncthreads();
-  int cur = 0;
-  for (int kk = 0; kk < K; kk += BK) {
-    const bool has_next = (kk + BK) < K;
-    if (has_next) load_regs(kk + BK, areg, breg);
-    char* a_lds_c = GB_ABUF(cur);
-    char* b_lds_c = GB_BBUF(cur);
-
-#pragma unroll
-    for (int ks = 0; ks < BK / 32; ++ks) {
-      // fragment k-range: lane kb = lane>>4 (4 groups of 8 elems)
-      const int kbyte = ks * 64 + (lane >> 4) * 16;
-      bf16x8 a_frag[MFRAG], b_frag[4];
-#pragma unroll
-      for (int m = 0; m < MFRAG; ++m) {
-        const int row = wm * (BMT / 2) + m * 16 + (lane & 15);
-        a_frag[m] = *reinterpret_cast<const bf16x8*>(a_lds_c + swz(row, kbyte));
-      }
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int row = wn * 64 + n * 16 + (lane & 15);
-        b_frag[n] = *reinterpret_cast<const bf16x8*>(b_lds_c + swz(row, kbyte));
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int m = 0; m < MFRAG; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[m], b_frag[n], acc[m][n], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    if (has_next) write_regs(GB_ABUF(cur ^ 1), GB_BBUF(cur ^ 1), areg, breg);
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef GB_ABUF
-#undef GB_BBUF
+  tile_regstaged_gemm<BMT, CT>(acc, smem, A1, A2, K1, W, N, K, COL, r0, c0);
 
   // epilogue: D mapping col = lane&15, row = (lane>>4)*4 + i
 #pragma unroll
@@ -176,24 +78,28 @@ void launch_gemm_bias2(const bf16* A1, const bf16* A2, const bf16* W,
                        const bf16* bias, const bf16* addend, long astride,
                        const bf16* addend2, long astride2, bf16* out, int N,
                        int K, int K1, int COL, hipStream_t stream) {
+  // tests/test_gpu_ggnn.py: test_fused_fwd_teacher_forced[small-64-2] and
+  // [small-192-2] take the column tail, every H = 128 case the aligned side
   if (COL % BN != 0) {  // column-tail variant, 32-row tile only
     const dim3 grid((N + 31) / 32, (COL + BN - 1) / BN);
-    const size_t lds = 2 * (32 + BN) * ROWB;
+    const size_t lds = tile_lds_bytes(32);
     hipLaunchKernelGGL((gemm_bias_kernel<32, true>), grid, dim3(256), lds,
                        stream, A1, A2, W, bias, addend, astride, addend2,
                        astride2, out, N, K, K1, COL);
     return;
   }
   const long blocks64 = (long)((N + BM - 1) / BM) * (COL / BN);
+  // tests/test_gpu_ggnn.py: test_fused_fwd_teacher_forced[small-128-3] takes
+  // the 32-row tile, test_gemm_bias_64row_tile the 64-row tile
   if (blocks64 < 384) {
     const dim3 grid((N + 31) / 32, COL / BN);
-    const size_t lds = 2 * (32 + BN) * ROWB;
+    const size_t lds = tile_lds_bytes(32);
     hipLaunchKernelGGL(gemm_bias_kernel<32>, grid, dim3(256), lds, stream, A1,
                        A2, W, bias, addend, astride, addend2, astride2, out, N,
                        K, K1, COL);
   } else {
     const dim3 grid((N + BM - 1) / BM, COL / BN);
-    const size_t lds = 2 * (BM + BN) * ROWB;
+    const size_t lds = tile_lds_bytes(BM);
     hipLaunchKernelGGL(gemm_bias_kernel<BM>, grid, dim3(256), lds, stream, A1,
                        A2, W, bias, addend, astride, addend2, astride2, out, N,
                        K, K1, COL);
@@ -220,6 +126,14 @@ void launch_gemm_bias(const bf16* A1, const bf16* A2, const bf16* W,
 
 __device__ __forceinline__ float sigf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
+#define GRU_TS 132  // floats per row of the fp32 gate tile
+
+// the gate tile reuses the pipeline's buffers once the K loop is done
+constexpr size_t gru_lds_bytes(int bmt) {
+  const size_t pipe = tile_lds_bytes(bmt), gate = bmt * GRU_TS * sizeof(float);
+  return pipe > gate ? pipe : gate;
+}
+
 template <int BMT>
 __global__ __launch_bounds__(256) void gemm_gru_kernel(
     const bf16* __restrict__ A1, const bf16* __restrict__ A2,
@@ -228,8 +142,6 @@ __global__ __launch_bounds__(256) void gemm_gru_kernel(
     bf16* __restrict__ R, bf16* __restrict__ Z, bf16* __restrict__ Nn,
     bf16* __restrict__ HN, int N, int K, int K1, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* a_lds = smem;
-  char* b_lds = smem + BMT * ROWB;
 
   const int r0 = blockIdx.x * BMT;
   const int c0 = blockIdx.y * BN;  // column block of the PERMUTED 4H space
@@ -241,83 +153,10 @@ __global__ __launch_bounds__(256) void gemm_gru_kernel(
 
   constexpr int MFRAG = BMT / 32;
   f32x4 acc[MFRAG][4] = {};
+  tile_regstaged_gemm<BMT, false>(acc, smem, A1, A2, K1, Wperm, N, K, 4 * H,
+                                  r0, c0);
 
-  // same T14 register double-buffering as gemm_bias_kernel above
-  const int srow = tid >> 3;
-  const int soff = (tid & 7) * 16;
-  constexpr int NAR = BMT / 32;
-  auto load_regs = [&](int kk, uint4v ar[NAR], uint4v br[4]) {
-#pragma unroll
-    for (int p = 0; p < NAR; ++p) {
-      const int rr = srow + p * 32;
-      const int gr = r0 + rr;
-      ar[p] = {};
-      if (gr < N) {
-        const int gk = kk + soff / 2;
-        const bf16* src = (gk < K1) ? (A1 + (long)gr * K1 + gk)
-                                    : (A2 + (long)gr * (K - K1) + (gk - K1));
-        ar[p] = *reinterpret_cast<const uint4v*>(src);
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int rr = srow + p * 32;
-      br[p] = *reinterpret_cast<const uint4v*>(Wperm + (long)(c0 + rr) * K +
-                                               kk + soff / 2);
-    }
-  };
-  auto write_regs = [&](char* ab, char* bb, const uint4v ar[NAR],
-                        const uint4v br[4]) {
-#pragma unroll
-    for (int p = 0; p < NAR; ++p)
-      *reinterpret_cast<uint4v*>(ab + swz(srow + p * 32, soff)) = ar[p];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      *reinterpret_cast<uint4v*>(bb + swz(srow + p * 32, soff)) = br[p];
-  };
-#define GB_ABUF(i) (a_lds + (i) * (BMT + BN) * ROWB)
-#define GB_BBUF(i) (b_lds + (i) * (BMT + BN) * ROWB)
-  uint4v areg[NAR], breg[4];
-  load_regs(0, areg, breg);
-  write_regs(GB_ABUF(0), GB_BBUF(0), areg, breg);
-  __syncthreads();
-  int cur = 0;
-  for (int kk = 0; kk < K; kk += BK) {
-    const bool has_next = (kk + BK) < K;
-    if (has_next) load_regs(kk + BK, areg, breg);
-    char* a_lds_c = GB_ABUF(cur);
-    char* b_lds_c = GB_BBUF(cur);
-#pragma unroll
-    for (int ks = 0; ks < BK / 32; ++ks) {
-      const int kbyte = ks * 64 + (lane >> 4) * 16;
-      bf16x8 a_frag[MFRAG], b_frag[4];
-#pragma unroll
-      for (int m = 0; m < MFRAG; ++m) {
-        const int row = wm * (BMT / 2) + m * 16 + (lane & 15);
-        a_frag[m] = *reinterpret_cast<const bf16x8*>(a_lds_c + swz(row, kbyte));
-      }
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int row = wn * 64 + n * 16 + (lane & 15);
-        b_frag[n] = *reinterpret_cast<const bf16x8*>(b_lds_c + swz(row, kbyte));
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int m = 0; m < MFRAG; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[m], b_frag[n], acc[m][n], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    if (has_next) write_regs(GB_ABUF(cur ^ 1), GB_BBUF(cur ^ 1), areg, breg);
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef GB_ABUF
-#undef GB_BBUF
-
-  // bounce fp32 gate pre-activations (+bias) through LDS, row stride 132
+  // bounce fp32 gate pre-activations (+bias) through LDS, row stride GRU_TS
   float* tile = reinterpret_cast<float*>(smem);
 #pragma unroll
   for (int m = 0; m < MFRAG; ++m) {
@@ -328,7 +167,7 @@ __global__ __launch_bounds__(256) void gemm_gru_kernel(
       const float b = __bfloat162float(bperm[c0 + col]);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        tile[(row + i) * 132 + col] = acc[m][n][i] + b;
+        tile[(row + i) * GRU_TS + col] = acc[m][n][i] + b;
     }
   }
   __syncthreads();
@@ -341,7 +180,7 @@ __global__ __launch_bounds__(256) void gemm_gru_kernel(
     const int jj = it & 31;
     const int gr = r0 + row;
     if (gr >= N) continue;
-    const f32x4 gse = *reinterpret_cast<const f32x4*>(tile + row * 132 + jj * 4);
+    const f32x4 gse = *reinterpret_cast<const f32x4*>(tile + row * GRU_TS + jj * 4);
     const float r = sigf_(gse[0]);
     const float z = sigf_(gse[1]);
     const float n = tanhf(gse[2] + r * gse[3]);
@@ -361,14 +200,16 @@ void launch_gemm_gru(const bf16* A1, const bf16* A2, const bf16* Wperm,
                      hipStream_t stream) {
   const int COL = 4 * H;
   const long blocks64 = (long)((N + BM - 1) / BM) * (COL / BN);
+  // tests/test_gpu_ggnn.py: test_fused_fwd_teacher_forced[small-128-3] takes
+  // the 32-row tile, [n24577-128-1] and [n6081-128-2] the 64-row tile
   if (blocks64 < 384) {
     const dim3 grid((N + 31) / 32, COL / BN);
-    const size_t lds = max((size_t)2 * (32 + BN) * ROWB, (size_t)32 * 132 * 4);
+    const size_t lds = gru_lds_bytes(32);
     hipLaunchKernelGGL(gemm_gru_kernel<32>, grid, dim3(256), lds, stream, A1,
                        A2, Wperm, bperm, h_in, h_new, R, Z, Nn, HN, N, K, K1, H);
   } else {
     const dim3 grid((N + BM - 1) / BM, COL / BN);
-    const size_t lds = max((size_t)2 * (BM + BN) * ROWB, (size_t)BM * 132 * 4);
+    const size_t lds = gru_lds_bytes(BM);
     hipLaunchKernelGGL(gemm_gru_kernel<BM>, grid, dim3(256), lds, stream, A1,
                        A2, Wperm, bperm, h_in, h_new, R, Z, Nn, HN, N, K, K1, H);
   }

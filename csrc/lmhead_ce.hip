@@ -1,7 +1,7 @@
 // K21: fused LM-head GEMM + cross-entropy over vocab 32100 (CodeT5),
 // MI355X (gfx950).
 //
-// Reference call site: /root/reference/CodeT5/models.py:140-149 — the T5
+// Reference call site: CodeT5 models.py, the seq2seq loss — the T5
 // teacher-forcing step computes logits (b*512, 32100) and CE over them;
 // torch materializes the fp32 logits (526 MB at b=8) plus fp32 dlogits in
 // the backward. Here the forward computes online logsumexp per row while
@@ -15,25 +15,20 @@
 // Vp % 128 == 0 (W padded with zero rows to Vp; cols >= V are masked).
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-#define WAVE 64
+#include "mfma_tile.h"
+
 #define CE_BM 128
-#define CE_BN 128
-#define CE_BK 64
-#define CE_ROWB 128       // bytes per LDS row (64 bf16)
+#define CE_BN TILE_BN
+#define CE_BK TILE_BK
 #define CE_CTILES 8       // vocab c-tiles (of 128) per workgroup chunk
 
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ int ce_swz(int row, int byte) {
-  return row * CE_ROWB + (byte ^ ((row & 7) << 4));
-}
-
-// one 128x64 bf16 tile -> LDS via global_load_lds (same staging as
-// gemm_bf16.hip g2_stage, 4 KiB pieces per wave)
+// one 128x64 bf16 tile -> LDS via global_load_lds, 4 1-KiB pieces per wave.
+// This file keeps its own copy of the glds stage and main loop of
+// mfma_tile.h (tile_glds_stage<4>, tile_glds_gemm<128>): routed through the
+// shared loop the forward ran 2.8 % slower (0.7 % through the shared stage
+// and k-step under its own loop) with the same instruction counts, and the
+// cause was not found. It shares the aliases, tile_swz and the LDS layout.
 __device__ __forceinline__ void ce_stage(const bf16* __restrict__ src_base,
                                          long row_stride_elems, int kk,
                                          char* lds, int wid, int lane) {
@@ -42,7 +37,7 @@ __device__ __forceinline__ void ce_stage(const bf16* __restrict__ src_base,
     const int c = wid * 4 + c4;
     const int row = 8 * c + (lane >> 3);
     const int kbyte = (lane & 7) * 16;
-    const int src_byte = kbyte ^ ((row & 7) << 4);
+    const int src_byte = tile_swz_byte(row, kbyte);
     const bf16* gsrc = src_base + row * row_stride_elems + kk + src_byte / 2;
     __builtin_amdgcn_global_load_lds(
         reinterpret_cast<const unsigned int*>(gsrc),
@@ -50,10 +45,16 @@ __device__ __forceinline__ void ce_stage(const bf16* __restrict__ src_base,
   }
 }
 
-#define CE_ABUF(i) (smem + (i) * (16384 + 16384))
-#define CE_BBUF(i) (smem + 16384 + (i) * (16384 + 16384))
-#define CE_TILE (smem + 2 * (16384 + 16384))  // fp32 [128][132]
+// LDS: the two (A | B) buffer pairs of mfma_tile.h, then the fp32 logits
+// tile [CE_BM][CE_TS], then the forward's per-row reduction scratch
+#define CE_ABUF(i) (smem + (i) * tile_pair_bytes(CE_BM))
+#define CE_BBUF(i) (smem + CE_BM * TILE_ROWB + (i) * tile_pair_bytes(CE_BM))
+#define CE_TILE (smem + tile_lds_bytes(CE_BM))
 #define CE_TS 132
+#define CE_RED_FLOATS 1024
+constexpr size_t ce_lds_bytes() {
+  return tile_lds_bytes(CE_BM) + (CE_TS * CE_BM + CE_RED_FLOATS) * sizeof(float);
+}
 
 // compute the 128x128 logits tile (r0, c0) into acc and spill fp32 to
 // CE_TILE (row stride CE_TS floats). Shared by fwd and bwd kernels.
@@ -81,12 +82,12 @@ __device__ __forceinline__ void ce_tile_gemm(
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         const int brow = wn * 64 + f * 16 + (lane & 15);
-        b_frag[f] = *reinterpret_cast<const bf16x8*>(CE_BBUF(cur) + ce_swz(brow, kbyte));
+        b_frag[f] = *reinterpret_cast<const bf16x8*>(CE_BBUF(cur) + tile_swz(brow, kbyte));
       }
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         const int arow = wm * 64 + f * 16 + (lane & 15);
-        a_frag[f] = *reinterpret_cast<const bf16x8*>(CE_ABUF(cur) + ce_swz(arow, kbyte));
+        a_frag[f] = *reinterpret_cast<const bf16x8*>(CE_ABUF(cur) + tile_swz(arow, kbyte));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_setprio(1);
@@ -262,7 +263,7 @@ void launch_lmhead_ce_fwd(const bf16* A, const bf16* W, const int* targets,
                           float* pmax, float* psum, float* ptgt, float* lse,
                           float* loss, int n_chunks, hipStream_t stream) {
   const dim3 grid(M / CE_BM, n_chunks);
-  const size_t shmem = 2 * (16384 + 16384) + (CE_TS * CE_BM + 1024) * 4;
+  const size_t shmem = ce_lds_bytes();
   hipLaunchKernelGGL(lmhead_ce_fwd_kernel, grid, dim3(256), shmem, stream, A, W,
                      targets, scale, K, V, Vp, n_chunks, pmax, psum, ptgt);
   const int tpb = 256;
@@ -276,7 +277,7 @@ void launch_lmhead_ce_bwd(const bf16* A, const bf16* W, const int* targets,
                           long M, int K, int V, int Vp, bf16* dlogits,
                           hipStream_t stream) {
   const dim3 grid(M / CE_BM, Vp / CE_BN);
-  const size_t shmem = 2 * (16384 + 16384) + (CE_TS * CE_BM + 1024) * 4;
+  const size_t shmem = ce_lds_bytes();
   hipLaunchKernelGGL(lmhead_ce_bwd_kernel, grid, dim3(256), shmem, stream, A, W,
                      targets, lse, gscale, scale, K, V, Vp, dlogits);
 }

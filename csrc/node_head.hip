@@ -8,10 +8,11 @@
 //
 // Geometry is fixed: h, fe are (N,128), every hidden width is 256. Tile
 // conventions follow gemm_bias.hip: 256-thread blocks, BK = 64 slices,
-// v_mfma_f32_16x16x32_bf16, XOR-swizzled LDS rows (swz), register-staged
-// double-buffered weight slices. A block owns BMT rows x all 256 columns
-// (4 column-waves of 64 columns), so a layer's bias+ReLU'd output tile can
-// be written back to LDS as the next layer's A operand; the (N,256)
+// v_mfma_f32_16x16x32_bf16, XOR-swizzled LDS rows (tile_swz),
+// register-staged double-buffered weight slices; the swizzle, the k-step and
+// the weight-slice staging come from mfma_tile.h. A block owns BMT rows x
+// all 256 columns (4 column-waves of 64 columns), so a layer's bias+ReLU'd
+// output tile can be written back to LDS as the next layer's A operand; the (N,256)
 // concatenation and the inter-layer activations never round-trip through
 // HBM on the forward's critical path. The two layers' eight weight slices
 // are streamed as ONE pipeline: the last slice of a layer prefetches the
@@ -22,51 +23,26 @@
 // one static array.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-#define WAVE 64
-
-using bf16 = __hip_bfloat16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using uint4v = __attribute__((ext_vector_type(4))) unsigned int;
+#include "mfma_tile.h"
 
 #define NH_D 256                  // hidden width (= 2 x 128 inputs)
 #define NH_DH 128                 // width of each input half
-#define NH_BK 64
-#define NH_ROWB (NH_BK * 2)       // bytes per LDS row (64 bf16)
+#define NH_BK TILE_BK
+#define NH_ROWB TILE_ROWB         // bytes per LDS row (64 bf16)
 #define NH_WBUF (NH_D * NH_ROWB)  // one weight slice: 256 rows = 32 KiB
 #define NH_NSL (NH_D / NH_BK)     // k-slices per layer
-
-// same swizzle as gemm_bias.hip (cdna_hip_programming.md T2)
-__device__ __forceinline__ int nh_swz(int row, int byte) {
-  return row * NH_ROWB + (byte ^ ((row & 7) << 4));
-}
 
 union nh_pack8 {
   uint4v v;
   bf16 e[8];
 };
 
-// weight-slice staging: thread (tid>>3, tid&7) moves the 16-B chunk
-// (tid&7) of rows (tid>>3) + 32p, p < 8, of W[:, kk:kk+64]
+// weight-slice staging (mfma_tile.h register staging, 8 row groups): the
+// 256 rows of W[:, kk:kk+64], W in (out, in) layout with NH_D columns
 __device__ __forceinline__ void nh_w_load(const bf16* __restrict__ W, int kk,
                                           int tid, uint4v r[8]) {
-  const int srow = tid >> 3;
-  const int soff = (tid & 7) * 16;
-#pragma unroll
-  for (int p = 0; p < 8; ++p)
-    r[p] = *reinterpret_cast<const uint4v*>(W + (long)(srow + p * 32) * NH_D +
-                                            kk + soff / 2);
-}
-
-__device__ __forceinline__ void nh_w_store(char* wb, int tid,
-                                           const uint4v r[8]) {
-  const int srow = tid >> 3;
-  const int soff = (tid & 7) * 16;
-#pragma unroll
-  for (int p = 0; p < 8; ++p)
-    *reinterpret_cast<uint4v*>(wb + nh_swz(srow + p * 32, soff)) = r[p];
+  tile_w_load<8>(W, NH_D, 0, kk, NH_D, tid, r);
 }
 
 // acc(BMT x 64 per wave) = act(BMT x 256) @ W(256 x 256)^T, W in
@@ -92,28 +68,8 @@ __device__ __forceinline__ void nh_layer_gemm(
     if (Wp) nh_w_load(Wp, kn, tid, wr);
     const char* a_s = act + s * BMT * NH_ROWB;
     const char* b_s = wbuf + cur * NH_WBUF;
-#pragma unroll
-    for (int ks = 0; ks < NH_BK / 32; ++ks) {
-      const int kbyte = ks * 64 + (lane >> 4) * 16;
-      bf16x8 a_frag[MF], b_frag[4];
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-        a_frag[m] = *reinterpret_cast<const bf16x8*>(
-            a_s + nh_swz(m * 16 + (lane & 15), kbyte));
-#pragma unroll
-      for (int n = 0; n < 4; ++n)
-        b_frag[n] = *reinterpret_cast<const bf16x8*>(
-            b_s + nh_swz(wn * 64 + n * 16 + (lane & 15), kbyte));
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int m = 0; m < MF; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[m], b_frag[n], acc[m][n], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    if (Wp) nh_w_store(wbuf + (cur ^ 1) * NH_WBUF, tid, wr);
+    tile_kstep<false>(acc, a_s, 0, b_s, wn * 64, lane);
+    if (Wp) tile_regs_store<8>(wbuf + (cur ^ 1) * NH_WBUF, tid, wr);
     __syncthreads();
     cur ^= 1;
   }
@@ -134,7 +90,7 @@ __device__ __forceinline__ void nh_acc_to_act(const f32x4 (&acc)[BMT / 16][4],
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = m * 16 + (lane >> 4) * 4 + i;
-        *reinterpret_cast<bf16*>(a_s + nh_swz(row, byte)) =
+        *reinterpret_cast<bf16*>(a_s + tile_swz(row, byte)) =
             __float2bfloat16(acc[m][n][i]);
       }
     }
@@ -154,7 +110,7 @@ __device__ __forceinline__ void nh_act_to_global(const char* act,
     const int gr = r0 + row;
     if (gr >= N) continue;
     const uint4v v = *reinterpret_cast<const uint4v*>(
-        act + (c >> 3) * BMT * NH_ROWB + nh_swz(row, (c & 7) * 16));
+        act + (c >> 3) * BMT * NH_ROWB + tile_swz(row, (c & 7) * 16));
     bf16* dst;
     if (out2 == nullptr)
       dst = out1 + (long)gr * NH_D + c * 8;
@@ -200,9 +156,9 @@ __global__ __launch_bounds__(256) void node_head_fwd_kernel(
       if (save) *reinterpret_cast<uint4v*>(X + (long)gr * NH_D + c * 8) = v;
     }
     *reinterpret_cast<uint4v*>(act + (c >> 3) * BMT * NH_ROWB +
-                               nh_swz(row, (c & 7) * 16)) = v;
+                               tile_swz(row, (c & 7) * 16)) = v;
   }
-  nh_w_store(wbuf, tid, wr);
+  tile_regs_store<8>(wbuf, tid, wr);
   __syncthreads();
 
   int cur = 0;
@@ -314,13 +270,13 @@ __global__ __launch_bounds__(256) void node_head_bwd_kernel(
         *reinterpret_cast<uint4v*>(dH2 + (long)gr * NH_D + c * 8) = o.v;
       }
       *reinterpret_cast<uint4v*>(act + (c >> 3) * BMT * NH_ROWB +
-                                 nh_swz(row, (c & 7) * 16)) = o.v;
+                                 tile_swz(row, (c & 7) * 16)) = o.v;
     }
     // weight buffer 1 is idle until the first slice's prefetch lands in it
     float* scr = reinterpret_cast<float*>(wbuf + NH_WBUF);
 #pragma unroll
     for (int j = 0; j < 8; ++j) scr[rg * NH_D + c * 8 + j] = dw[j];
-    nh_w_store(wbuf, tid, wr);
+    tile_regs_store<8>(wbuf, tid, wr);
     __syncthreads();
     float s = 0.f;
 #pragma unroll

@@ -32,6 +32,9 @@ ext = CUDAExtension(
         "csrc/node_head.hip",
         "csrc/graph_head.hip",
     ],
+    # the shared tile core is included by gemm_bias, gemm_bf16, lmhead_ce and
+    # node_head: editing it rebuilds the extension
+    depends=["csrc/mfma_tile.h"],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
         "nvcc": ["-O3", "-std=c++17"],

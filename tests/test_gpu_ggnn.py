@@ -76,6 +76,7 @@ import pytest
 import torch
 
 import ggnn_oracle as O
+from oracle_checks import assert_within as _assert_within
 
 pytestmark = pytest.mark.gpu
 
@@ -98,18 +99,6 @@ def _ext():
 
 def _u(dtype):
     return U16 if dtype == torch.bfloat16 else 0.0
-
-
-def _assert_within(got, ref, bound, what):
-    """Every element: |got - ref| <= bound. Non-finite values fail."""
-    got = got.double()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
-    excess = (got - ref).abs() - bound
-    worst = int(excess.argmax())
-    assert float(excess.flatten()[worst]) <= 0.0, (
-        f"{what}: element {worst} got {float(got.flatten()[worst])!r} "
-        f"ref {float(ref.flatten()[worst])!r} bound {float(bound.flatten()[worst])!r}")
 
 
 # --------------------------------------------------------------------------

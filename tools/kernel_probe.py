@@ -40,6 +40,16 @@ Dt = torch.empty(B, H, L, device=dev)
 xff = torch.randn(N, FF, device=dev, dtype=bf)
 _, lnm, lnr = ext.layernorm_fwd(x, b32, b32, 1e-5)
 
+# LM head + cross-entropy (CodeT5 vocabulary), half a b=8 teacher-forcing step
+CE_M, CE_V = 4096, 32100
+CE_VP = (CE_V + 127) // 128 * 128
+ce_h = torch.randn(CE_M, D, device=dev, dtype=bf) * 0.3
+ce_w = torch.zeros(CE_VP, D, device=dev, dtype=bf)
+ce_w[:CE_V] = torch.randn(CE_V, D, device=dev, dtype=bf) * 0.3
+ce_t = torch.randint(0, CE_V, (CE_M,), device=dev, dtype=torch.int32)
+ce_g = torch.full((CE_M,), 1.0 / CE_M, device=dev)
+_, ce_lse = ext.lmhead_ce_fwd(ce_h, ce_w, ce_t, D ** -0.5, CE_V)
+
 wf32 = w.float()
 xf32 = x.float()
 dyf32 = dy.float()
@@ -61,6 +71,10 @@ variants = {
     "layernorm fwd (8192x768)": lambda: ext.layernorm_fwd(x, b32, b32, 1e-5),
     "layernorm bwd": lambda: ext.layernorm_bwd(dy, x, b32, lnm, lnr),
     "layernorm wgrad": lambda: ext.layernorm_wgrad(dy, x, lnm, lnr),
+    "lmhead_ce_fwd (4096x768 V32100)": lambda: ext.lmhead_ce_fwd(
+        ce_h, ce_w, ce_t, D ** -0.5, CE_V),
+    "lmhead_ce_bwd (4096x768 V32100)": lambda: ext.lmhead_ce_bwd(
+        ce_h, ce_w, ce_t, ce_lse, ce_g, D ** -0.5, CE_V),
     "copy 50MB (roofline ref)": lambda: xff.clone(),
 }
 
