@@ -7,6 +7,8 @@
 #include <c10/hip/HIPStream.h>
 #include <c10/util/accumulate.h>
 
+#include <climits>
+
 // the launchers are defined (at global scope) in flowgnn_kernels.hip
 template <typename T>
 void launch_embed4_fwd(const T*, const long*, T*, int, int, hipStream_t);
@@ -578,6 +580,8 @@ std::vector<at::Tensor> gru_gates2_bwd(at::Tensor grad_h_new, at::Tensor h, at::
 
 at::Tensor colsum(at::Tensor x, c10::optional<at::Tensor> out_opt) {
   CHECK_GPU(x);
+  TORCH_CHECK(x.dim() == 2, "colsum: x must be (N, C)");
+  TORCH_CHECK(x.size(0) <= INT_MAX && x.size(1) <= INT_MAX, "colsum: extent exceeds int");
   auto out = acc_or_zeros(out_opt, {x.size(1)}, x.options(), "colsum");
   dispatch_float_bf16(x, "colsum", [&](auto tag) {
     using T = decltype(tag);
@@ -591,12 +595,39 @@ at::Tensor colsum(at::Tensor x, c10::optional<at::Tensor> out_opt) {
 // Transformer kernels (csrc/transformer_kernels.hip)
 // ---------------------------------------------------------------------------
 
+// Argument checks shared by every binding of this family. The kernels index
+// raw pointers, so each tensor argument is held to: contiguous, on the lead
+// tensor's device, the expected dtype and the expected shape.
+static constexpr size_t kLdsLimit = 64 * 1024;  // dynamic LDS without opt-in
+
+static void tk_lead(const char* op, const at::Tensor& x, bool rows = true) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), op, ": lead tensor must be a contiguous GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, op,
+              ": unsupported dtype ", x.scalar_type());
+  // the row kernels divide by the last dimension; the flat elementwise ones
+  // (rows = false) take any shape, an empty one included
+  TORCH_CHECK(!rows || (x.dim() >= 1 && x.size(-1) > 0), op,
+              ": needs a non-empty last dimension");
+}
+
+static void tk_arg(const char* op, const char* name, const at::Tensor& t, const at::Tensor& lead,
+                   at::ScalarType dt, at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == lead.device(), op, ": ", name,
+              " must be on the lead tensor's GPU");
+  TORCH_CHECK(t.scalar_type() == dt, op, ": ", name, " must have dtype ", dt, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  TORCH_CHECK(t.sizes() == shape, op, ": ", name, " must have shape ", shape, ", got ",
+              t.sizes());
+}
+
 std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor gamma, at::Tensor beta,
                                       double eps) {
-  CHECK_GPU(x);
-  TORCH_CHECK(gamma.scalar_type() == at::kFloat && beta.scalar_type() == at::kFloat);
+  tk_lead("layernorm_fwd", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("layernorm_fwd", "gamma", gamma, x, at::kFloat, {D});
+  tk_arg("layernorm_fwd", "beta", beta, x, at::kFloat, {D});
   auto y = at::empty_like(x);
   auto mean = at::empty({N}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
@@ -611,9 +642,13 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor gamma, at::Tensor
 
 at::Tensor layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor gamma, at::Tensor mean,
                          at::Tensor rstd) {
-  CHECK_GPU(dy);
+  tk_lead("layernorm_bwd", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("layernorm_bwd", "dy", dy, x, x.scalar_type(), x.sizes());
+  tk_arg("layernorm_bwd", "gamma", gamma, x, at::kFloat, {D});
+  tk_arg("layernorm_bwd", "mean", mean, x, at::kFloat, {N});
+  tk_arg("layernorm_bwd", "rstd", rstd, x, at::kFloat, {N});
   auto dx = at::empty_like(x);
   dispatch_float_bf16(x, "layernorm_bwd", [&](auto tag) {
     using T = decltype(tag);
@@ -626,8 +661,12 @@ at::Tensor layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor gamma, at::Tens
 
 std::vector<at::Tensor> layernorm_wgrad(at::Tensor dy, at::Tensor x, at::Tensor mean,
                                         at::Tensor rstd) {
+  tk_lead("layernorm_wgrad", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("layernorm_wgrad", "dy", dy, x, x.scalar_type(), x.sizes());
+  tk_arg("layernorm_wgrad", "mean", mean, x, at::kFloat, {N});
+  tk_arg("layernorm_wgrad", "rstd", rstd, x, at::kFloat, {N});
   auto dgamma = at::zeros({D}, x.options().dtype(at::kFloat));
   auto dbeta = at::zeros({D}, x.options().dtype(at::kFloat));
   dispatch_float_bf16(x, "layernorm_wgrad", [&](auto tag) {
@@ -639,12 +678,20 @@ std::vector<at::Tensor> layernorm_wgrad(at::Tensor dy, at::Tensor x, at::Tensor 
   return {dgamma, dbeta};
 }
 
-at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
-  CHECK_GPU(x);
-  TORCH_CHECK(bias.scalar_type() == at::kFloat);
+// D: a multiple of the 16-B vector, and the fp32 bias row must fit in LDS
+static int check_bias_gelu_geom(const char* op, const at::Tensor& x, const at::Tensor& bias) {
+  tk_lead(op, x);
   const int D = x.size(-1);
-  TORCH_CHECK(D % (x.scalar_type() == at::kFloat ? 4 : 8) == 0,
-              "bias_gelu: D must be a multiple of the 16-B vector width");
+  TORCH_CHECK(D % (x.scalar_type() == at::kFloat ? 4 : 8) == 0, op,
+              ": D must be a multiple of the 16-B vector width");
+  TORCH_CHECK((size_t)D * sizeof(float) <= kLdsLimit, op, ": D = ", D,
+              " exceeds the LDS-staged bias row (", kLdsLimit / sizeof(float), ")");
+  tk_arg(op, "bias", bias, x, at::kFloat, {D});
+  return D;
+}
+
+at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
+  const int D = check_bias_gelu_geom("bias_gelu_fwd", x, bias);
   auto y = at::empty_like(x);
   dispatch_float_bf16(x, "bias_gelu_fwd", [&](auto tag) {
     using T = decltype(tag);
@@ -655,8 +702,8 @@ at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
 }
 
 at::Tensor bias_gelu_bwd(at::Tensor dy, at::Tensor x, at::Tensor bias) {
-  CHECK_GPU(dy);
-  const int D = x.size(-1);
+  const int D = check_bias_gelu_geom("bias_gelu_bwd", x, bias);
+  tk_arg("bias_gelu_bwd", "dy", dy, x, x.scalar_type(), x.sizes());
   auto dx = at::empty_like(x);
   dispatch_float_bf16(x, "bias_gelu_bwd", [&](auto tag) {
     using T = decltype(tag);
@@ -676,7 +723,8 @@ static void check_softmax_geom(const at::Tensor& t, int L) {
 std::vector<at::Tensor> softmax_mask_fwd(at::Tensor S, c10::optional<at::Tensor> valid,
                                          double scale, double dropout_p, int64_t seed,
                                          bool causal) {
-  CHECK_GPU(S);
+  tk_lead("softmax_mask_fwd", S);
+  TORCH_CHECK(S.dim() >= 2, "softmax_mask_fwd: S must be (..., Lq, L)");
   const int L = S.size(-1);
   const long R = S.numel() / L;
   check_softmax_geom(S, L);
@@ -688,9 +736,13 @@ std::vector<at::Tensor> softmax_mask_fwd(at::Tensor S, c10::optional<at::Tensor>
   const int* vptr = nullptr;
   int rows_per_batch = 1;
   if (valid.has_value()) {
-    TORCH_CHECK(valid->scalar_type() == at::kInt);
+    const long nb = valid->numel();
+    TORCH_CHECK(valid->dim() == 1 && nb > 0 && R % nb == 0,
+                "softmax_mask_fwd: valid must be 1-D and its length must divide the ", R,
+                " rows");
+    tk_arg("softmax_mask_fwd", "valid", *valid, S, at::kInt, {nb});
     vptr = valid->data_ptr<int>();
-    rows_per_batch = (int)(R / valid->size(0));
+    rows_per_batch = (int)(R / nb);
   }
   dispatch_float_bf16(S, "softmax_mask_fwd", [&](auto tag) {
     using T = decltype(tag);
@@ -704,7 +756,8 @@ std::vector<at::Tensor> softmax_mask_fwd(at::Tensor S, c10::optional<at::Tensor>
 
 at::Tensor softmax_mask_bwd(at::Tensor dPd, at::Tensor P, double scale, double dropout_p,
                             int64_t seed) {
-  CHECK_GPU(dPd);
+  tk_lead("softmax_mask_bwd", P);
+  tk_arg("softmax_mask_bwd", "dPd", dPd, P, P.scalar_type(), P.sizes());
   const int L = P.size(-1);
   const long R = P.numel() / L;
   check_softmax_geom(P, L);
@@ -719,10 +772,10 @@ at::Tensor softmax_mask_bwd(at::Tensor dPd, at::Tensor P, double scale, double d
 
 
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor gamma, double eps) {
-  CHECK_GPU(x);
-  TORCH_CHECK(gamma.scalar_type() == at::kFloat);
+  tk_lead("rmsnorm_fwd", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("rmsnorm_fwd", "gamma", gamma, x, at::kFloat, {D});
   auto y = at::empty_like(x);
   auto rstd = at::empty({N}, x.options().dtype(at::kFloat));
   dispatch_float_bf16(x, "rmsnorm_fwd", [&](auto tag) {
@@ -734,9 +787,12 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor gamma, double eps) 
 }
 
 at::Tensor rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor gamma, at::Tensor rstd) {
-  CHECK_GPU(dy);
+  tk_lead("rmsnorm_bwd", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("rmsnorm_bwd", "dy", dy, x, x.scalar_type(), x.sizes());
+  tk_arg("rmsnorm_bwd", "gamma", gamma, x, at::kFloat, {D});
+  tk_arg("rmsnorm_bwd", "rstd", rstd, x, at::kFloat, {N});
   auto dx = at::empty_like(x);
   dispatch_float_bf16(x, "rmsnorm_bwd", [&](auto tag) {
     using T = decltype(tag);
@@ -748,8 +804,11 @@ at::Tensor rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor gamma, at::Tensor
 
 at::Tensor rmsnorm_wgrad(at::Tensor dy, at::Tensor x, at::Tensor rstd,
                          c10::optional<at::Tensor> out_opt) {
+  tk_lead("rmsnorm_wgrad", x);
   const int D = x.size(-1);
   const long N = x.numel() / D;
+  tk_arg("rmsnorm_wgrad", "dy", dy, x, x.scalar_type(), x.sizes());
+  tk_arg("rmsnorm_wgrad", "rstd", rstd, x, at::kFloat, {N});
   auto dgamma = acc_or_zeros(out_opt, {D}, x.options(), "rmsnorm_wgrad");
   dispatch_float_bf16(x, "rmsnorm_wgrad", [&](auto tag) {
     using T = decltype(tag);
@@ -1328,19 +1387,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lmhead_ce_fwd", &lmhead_ce_fwd);
   m.def("lmhead_ce_bwd", &lmhead_ce_bwd);
   m.def("relbias_wgrad", [](at::Tensor dbias, at::Tensor buckets, int64_t nb) {
-    CHECK_GPU(dbias);
-    TORCH_CHECK(dbias.scalar_type() == at::kFloat &&
-                buckets.scalar_type() == at::kInt && buckets.is_contiguous());
+    tk_lead("relbias_wgrad", dbias);
+    TORCH_CHECK(dbias.scalar_type() == at::kFloat, "relbias_wgrad: dbias must be fp32");
+    TORCH_CHECK(dbias.dim() >= 2 && dbias.size(0) > 0, "relbias_wgrad: dbias must be (H, ...)");
     const int H = dbias.size(0);
     const long QK = dbias.numel() / H;
-    TORCH_CHECK(buckets.numel() == QK);
+    // the kernel maps one head per lane of a 16-lane group
+    TORCH_CHECK(H <= 16, "relbias_wgrad: at most 16 heads, got ", H);
+    TORCH_CHECK(nb > 0 && (size_t)4 * nb * H * sizeof(float) <= kLdsLimit,
+                "relbias_wgrad: num_buckets * H exceeds the per-wave LDS partials");
+    TORCH_CHECK(buckets.numel() == QK, "relbias_wgrad: buckets must have ", QK, " entries");
+    tk_arg("relbias_wgrad", "buckets", buckets, dbias, at::kInt, buckets.sizes());
     auto dw = at::zeros({nb, (long)H}, dbias.options());
     launch_relbias_wgrad(dbias.data_ptr<float>(), buckets.data_ptr<int>(),
                          dw.data_ptr<float>(), QK, H, (int)nb, cur_stream());
     return dw;
   });
   m.def("relu_dropout_fwd", [](at::Tensor x, double p, int64_t seed) {
-    CHECK_GPU(x);
+    tk_lead("relu_dropout_fwd", x, false);
+    TORCH_CHECK(x.numel() % (x.scalar_type() == at::kFloat ? 4 : 8) == 0,
+                "relu_dropout: numel must be a multiple of the 16-B vector");
     auto out = at::empty_like(x);
     dispatch_float_bf16(x, "relu_dropout_fwd", [&](auto tag) {
       using T = decltype(tag);
@@ -1350,7 +1416,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return out;
   });
   m.def("relu_dropout_bwd", [](at::Tensor dy, at::Tensor x, double p, int64_t seed) {
-    CHECK_GPU(dy);
+    tk_lead("relu_dropout_bwd", dy, false);
+    TORCH_CHECK(dy.numel() % (dy.scalar_type() == at::kFloat ? 4 : 8) == 0,
+                "relu_dropout: numel must be a multiple of the 16-B vector");
+    tk_arg("relu_dropout_bwd", "x", x, dy, dy.scalar_type(), dy.sizes());
     auto dx = at::empty_like(dy);
     dispatch_float_bf16(dy, "relu_dropout_bwd", [&](auto tag) {
       using T = decltype(tag);
@@ -1360,9 +1429,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return dx;
   });
   m.def("dropout_add_fwd", [](at::Tensor h, at::Tensor res, double p, int64_t seed) {
-    CHECK_GPU(h);
-    CHECK_GPU(res);
-    TORCH_CHECK(h.numel() == res.numel());
+    tk_lead("dropout_add_fwd", h, false);
+    tk_arg("dropout_add_fwd", "res", res, h, h.scalar_type(), h.sizes());
     TORCH_CHECK(h.numel() % (h.scalar_type() == at::kFloat ? 4 : 8) == 0,
                 "dropout_add: numel must be a multiple of the 16-B vector");
     auto out = at::empty_like(h);
@@ -1374,7 +1442,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return out;
   });
   m.def("dropout_add_bwd", [](at::Tensor dy, double p, int64_t seed) {
-    CHECK_GPU(dy);
+    tk_lead("dropout_add_bwd", dy, false);
+    TORCH_CHECK(dy.numel() % (dy.scalar_type() == at::kFloat ? 4 : 8) == 0,
+                "dropout_add: numel must be a multiple of the 16-B vector");
     auto dh = at::empty_like(dy);
     dispatch_float_bf16(dy, "dropout_add_bwd", [&](auto tag) {
       using T = decltype(tag);
@@ -1385,11 +1455,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("ln_res_dropout_fwd", [](at::Tensor h, at::Tensor res, at::Tensor gamma,
                                  at::Tensor beta, double eps, double p, int64_t seed) {
-    CHECK_GPU(h);
-    CHECK_GPU(res);
+    tk_lead("ln_res_dropout_fwd", h);
     const int D = h.size(-1);
     TORCH_CHECK(D % 256 == 0, "ln_res_dropout: D must be a multiple of 256");
     const long N = h.numel() / D;
+    tk_arg("ln_res_dropout_fwd", "res", res, h, h.scalar_type(), h.sizes());
+    tk_arg("ln_res_dropout_fwd", "gamma", gamma, h, at::kFloat, {D});
+    tk_arg("ln_res_dropout_fwd", "beta", beta, h, at::kFloat, {D});
     auto y = at::empty_like(h);
     auto mean = at::empty({N}, h.options().dtype(at::kFloat));
     auto rstd = at::empty({N}, h.options().dtype(at::kFloat));
@@ -1406,9 +1478,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_res_dropout_bwd", [](at::Tensor dy, at::Tensor h, at::Tensor res,
                                  at::Tensor gamma, at::Tensor mean, at::Tensor rstd,
                                  double p, int64_t seed) {
-    CHECK_GPU(dy);
+    tk_lead("ln_res_dropout_bwd", dy);
     const int D = dy.size(-1);
+    TORCH_CHECK(D % 256 == 0, "ln_res_dropout: D must be a multiple of 256");
     const long N = dy.numel() / D;
+    tk_arg("ln_res_dropout_bwd", "h", h, dy, dy.scalar_type(), dy.sizes());
+    tk_arg("ln_res_dropout_bwd", "res", res, dy, dy.scalar_type(), dy.sizes());
+    tk_arg("ln_res_dropout_bwd", "gamma", gamma, dy, at::kFloat, {D});
+    tk_arg("ln_res_dropout_bwd", "mean", mean, dy, at::kFloat, {N});
+    tk_arg("ln_res_dropout_bwd", "rstd", rstd, dy, at::kFloat, {N});
     auto dz = at::empty_like(dy);
     auto dh = at::empty_like(dy);
     auto z = at::empty_like(dy);
@@ -1425,9 +1503,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_res_dropout_wgrad", [](at::Tensor dy, at::Tensor h, at::Tensor res,
                                    at::Tensor mean, at::Tensor rstd, double p,
                                    int64_t seed) {
-    CHECK_GPU(dy);
+    tk_lead("ln_res_dropout_wgrad", dy);
     const int D = dy.size(-1);
     const long N = dy.numel() / D;
+    tk_arg("ln_res_dropout_wgrad", "h", h, dy, dy.scalar_type(), dy.sizes());
+    tk_arg("ln_res_dropout_wgrad", "res", res, dy, dy.scalar_type(), dy.sizes());
+    tk_arg("ln_res_dropout_wgrad", "mean", mean, dy, at::kFloat, {N});
+    tk_arg("ln_res_dropout_wgrad", "rstd", rstd, dy, at::kFloat, {N});
     auto dgamma = at::zeros({(long)D}, dy.options().dtype(at::kFloat));
     auto dbeta = at::zeros({(long)D}, dy.options().dtype(at::kFloat));
     dispatch_float_bf16(dy, "ln_res_dropout_wgrad", [&](auto tag) {
@@ -1441,10 +1523,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("embed_scatter", [](at::Tensor dY, at::Tensor idx, long num_rows, long padding_idx,
                             c10::optional<at::Tensor> out_opt) {
-    CHECK_GPU(dY);
-    TORCH_CHECK(idx.scalar_type() == at::kLong && idx.is_contiguous());
+    tk_lead("embed_scatter", dY);
     const int D = dY.size(-1);
     const long N = dY.numel() / D;
+    TORCH_CHECK(idx.numel() == N, "embed_scatter: idx must have one entry per row of dY");
+    tk_arg("embed_scatter", "idx", idx, dY, at::kLong, idx.sizes());
     auto dW = acc_or_zeros(out_opt, {num_rows, (long)D}, dY.options(), "embed_scatter");
     dispatch_float_bf16(dY, "embed_scatter", [&](auto tag) {
       using T = decltype(tag);

@@ -14,6 +14,7 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+using std::max;
 using std::min;
 
 #define WAVE 64
@@ -72,6 +73,10 @@ __device__ __forceinline__ float wave_max(float v) {
 // LayerNorm: y = (x - mean) * rstd * gamma + beta  (per row of D)
 // ---------------------------------------------------------------------------
 
+// vector iterations of a row the forward kernels keep in registers between
+// their passes (mean, centred variance, output): D <= 4 * 256 = 1024
+#define LN_CACHE_IT 4
+
 template <typename T>
 __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
                                      const float* __restrict__ gamma,
@@ -84,33 +89,91 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
   if (row >= N) return;
   const T* xr = x + row * D;
   const bool vec = (D % (WAVE * 4) == 0);
-  float s = 0.f, s2 = 0.f;
+  // Mean from sums shifted by the row's first element (a constant row gives
+  // mu == x0 exactly), then a second pass centred on mu for the variance:
+  // the one-pass s2/D - mu*mu cancels catastrophically once |mean| >> std
+  // and can go negative.
+  const float x0 = tf(xr[0]);
+  T* yr = y + row * D;
+  if (vec && D <= LN_CACHE_IT * WAVE * 4) {
+    // the row stays in registers across the three passes: one read of x
+    f4 c[LN_CACHE_IT];
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      const int d = (it * WAVE + lane) * 4;
+      if (d < D) {
+        c[it] = load4(xr + d);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s += c[it].v[u] - x0;
+      }
+    }
+    const float mu = x0 + wave_sum(s) / D;
+    float s2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      if ((it * WAVE + lane) * 4 < D) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          c[it].v[u] -= mu;
+          s2 += c[it].v[u] * c[it].v[u];
+        }
+      }
+    }
+    const float rs = rsqrtf(wave_sum(s2) / D + eps);
+    if (lane == 0) {
+      mean[row] = mu;
+      rstd[row] = rs;
+    }
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      const int d = (it * WAVE + lane) * 4;
+      if (d < D) {
+        const f4 g = load4(gamma + d);
+        const f4 bb = load4(beta + d);
+        f4 o;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o.v[u] = c[it].v[u] * rs * g.v[u] + bb.v[u];
+        store4(yr + d, o);
+      }
+    }
+    return;
+  }
+  // wider or unaligned rows: the second and third pass re-read the row
+  // (L1/L2-resident)
+  float s = 0.f;
+  if (vec) {
+    for (int d = lane * 4; d < D; d += WAVE * 4) {
+      const f4 a = load4(xr + d);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s += a.v[u] - x0;
+    }
+  } else {
+    for (int d = lane; d < D; d += WAVE) s += tf(xr[d]) - x0;
+  }
+  const float mu = x0 + wave_sum(s) / D;
+  float s2 = 0.f;
   if (vec) {
     for (int d = lane * 4; d < D; d += WAVE * 4) {
       const f4 a = load4(xr + d);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        s += a.v[u];
-        s2 += a.v[u] * a.v[u];
+        const float c = a.v[u] - mu;
+        s2 += c * c;
       }
     }
   } else {
     for (int d = lane; d < D; d += WAVE) {
-      const float v = tf(xr[d]);
-      s += v;
-      s2 += v * v;
+      const float c = tf(xr[d]) - mu;
+      s2 += c * c;
     }
   }
-  s = wave_sum(s);
-  s2 = wave_sum(s2);
-  const float mu = s / D;
-  const float var = s2 / D - mu * mu;
+  const float var = wave_sum(s2) / D;  // a sum of squares: never negative
   const float rs = rsqrtf(var + eps);
   if (lane == 0) {
     mean[row] = mu;
     rstd[row] = rs;
   }
-  T* yr = y + row * D;
   if (vec) {
     for (int d = lane * 4; d < D; d += WAVE * 4) {
       const f4 a = load4(xr + d);
@@ -516,7 +579,8 @@ __global__ void softmax_mask_fwd_kernel(const T* __restrict__ S,
   const long row = (long)(blockIdx.x * (blockDim.x / WAVE)) + threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
   if (row >= R) return;
-  int vl = valid ? valid[row / rows_per_batch] : L;
+  // clamp: a valid[b] outside [0, L] would read past the row
+  int vl = valid ? max(0, min(valid[row / rows_per_batch], L)) : L;
   if (causal) vl = min(vl, (int)(row % Lq) + 1);
   const T* sr = S + row * L;
   constexpr int VEC = 16 / sizeof(T);  // one 16-B vector store per lane
@@ -827,7 +891,61 @@ __global__ void ln_res_dropout_fwd_kernel(
   if (row >= N) return;
   const T* hr = h + row * D;
   const T* rr = res + row * D;
-  float s = 0.f, s2 = 0.f;
+  // shifted mean + centred variance pass: see layernorm_fwd_kernel
+  const bool keep0 = (p8 == 0) || keep_mask(row * D, seed, p8);
+  const float z0 = (keep0 ? tf(hr[0]) * dscale : 0.f) + tf(rr[0]);
+  T* yr = y + row * D;
+  if (D <= LN_CACHE_IT * WAVE * 4) {
+    // z = dropout(h) + res is formed once (one hash, one read of h and res)
+    // and stays in registers across the three passes
+    f4 c[LN_CACHE_IT];
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      const int d = (it * WAVE + lane) * 4;
+      if (d < D) {
+        const f4 a = load4(hr + d);
+        const f4 b = load4(rr + d);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const bool keep = (p8 == 0) || keep_mask(row * D + d + u, seed, p8);
+          c[it].v[u] = (keep ? a.v[u] * dscale : 0.f) + b.v[u];
+          s += c[it].v[u] - z0;
+        }
+      }
+    }
+    const float mu = z0 + wave_sum(s) / D;
+    float s2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      if ((it * WAVE + lane) * 4 < D) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          c[it].v[u] -= mu;
+          s2 += c[it].v[u] * c[it].v[u];
+        }
+      }
+    }
+    const float rs = rsqrtf(wave_sum(s2) / D + eps);
+    if (lane == 0) {
+      mean[row] = mu;
+      rstd[row] = rs;
+    }
+#pragma unroll
+    for (int it = 0; it < LN_CACHE_IT; ++it) {
+      const int d = (it * WAVE + lane) * 4;
+      if (d < D) {
+        const f4 g = load4(gamma + d);
+        const f4 bb = load4(beta + d);
+        f4 o;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o.v[u] = c[it].v[u] * rs * g.v[u] + bb.v[u];
+        store4(yr + d, o);
+      }
+    }
+    return;
+  }
+  float s = 0.f;
   for (int d = lane * 4; d < D; d += WAVE * 4) {
     const f4 a = load4(hr + d);
     const f4 b = load4(rr + d);
@@ -835,19 +953,26 @@ __global__ void ln_res_dropout_fwd_kernel(
     for (int u = 0; u < 4; ++u) {
       const bool keep = (p8 == 0) || keep_mask(row * D + d + u, seed, p8);
       const float z = (keep ? a.v[u] * dscale : 0.f) + b.v[u];
-      s += z;
-      s2 += z * z;
+      s += z - z0;
     }
   }
-  s = wave_sum(s);
-  s2 = wave_sum(s2);
-  const float mu = s / D;
-  const float rs = rsqrtf(s2 / D - mu * mu + eps);
+  const float mu = z0 + wave_sum(s) / D;
+  float s2 = 0.f;
+  for (int d = lane * 4; d < D; d += WAVE * 4) {
+    const f4 a = load4(hr + d);
+    const f4 b = load4(rr + d);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool keep = (p8 == 0) || keep_mask(row * D + d + u, seed, p8);
+      const float c = (keep ? a.v[u] * dscale : 0.f) + b.v[u] - mu;
+      s2 += c * c;
+    }
+  }
+  const float rs = rsqrtf(wave_sum(s2) / D + eps);
   if (lane == 0) {
     mean[row] = mu;
     rstd[row] = rs;
   }
-  T* yr = y + row * D;
   for (int d = lane * 4; d < D; d += WAVE * 4) {
     const f4 a = load4(hr + d);
     const f4 b = load4(rr + d);
@@ -1177,8 +1302,9 @@ void launch_relu_dropout_fwd(const T* x, T* out, long total, float dropout_p,
   const float dscale = (p8 > 0) ? 256.0f / (256.0f - p8) : 1.0f;
   const int block = 256;
   const int grid = (int)min((total / VEC + block - 1) / block, (long)4096);
-  hipLaunchKernelGGL(relu_dropout_fwd_kernel<T>, dim3(grid), dim3(block), 0,
-                     stream, x, out, total, p8, seed, dscale);
+  if (grid)
+    hipLaunchKernelGGL(relu_dropout_fwd_kernel<T>, dim3(grid), dim3(block), 0,
+                       stream, x, out, total, p8, seed, dscale);
 }
 
 template <typename T>
@@ -1190,8 +1316,9 @@ void launch_relu_dropout_bwd(const T* dy, const T* x, T* dx, long total,
   const float dscale = (p8 > 0) ? 256.0f / (256.0f - p8) : 1.0f;
   const int block = 256;
   const int grid = (int)min((total / VEC + block - 1) / block, (long)4096);
-  hipLaunchKernelGGL(relu_dropout_bwd_kernel<T>, dim3(grid), dim3(block), 0,
-                     stream, dy, x, dx, total, p8, seed, dscale);
+  if (grid)
+    hipLaunchKernelGGL(relu_dropout_bwd_kernel<T>, dim3(grid), dim3(block), 0,
+                       stream, dy, x, dx, total, p8, seed, dscale);
 }
 
 template void launch_relu_dropout_fwd<__hip_bfloat16>(
@@ -1228,7 +1355,8 @@ __global__ void relbias_wgrad_kernel(const float* __restrict__ dbias,
     for (long qk = (long)blockIdx.x * (nwv * 4) + wv * 4 + qsub; qk < QK;
          qk += (long)gridDim.x * nwv * 4) {
       const int b = buckets[qk];
-      atomicAdd(mine + b * H + h, dbias[(long)h * QK + qk]);
+      // a bucket outside [0, NB) would write past this wave's partials
+      if ((unsigned)b < (unsigned)NB) atomicAdd(mine + b * H + h, dbias[(long)h * QK + qk]);
     }
   }
   __syncthreads();

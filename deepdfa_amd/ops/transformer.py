@@ -756,7 +756,9 @@ class _ReluDropout(torch.autograd.Function):
 
 
 def relu_dropout(x, p=0.0, training=True):
-    if x.is_cuda:
+    """dropout(relu(x)); fused on GPU when numel fills whole 16-B vectors,
+    torch composition elsewhere (as dropout_add)."""
+    if x.is_cuda and x.numel() % (4 if x.dtype == torch.float32 else 8) == 0:
         return _ReluDropout.apply(x, p, training)
     h = torch.relu(x)
     return torch.nn.functional.dropout(h, p) if (training and p > 0) else h
