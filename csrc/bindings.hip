@@ -94,6 +94,9 @@ void launch_flash_dkv(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_
 template <typename T>
 void launch_softmax_mask_bwd(const T*, const T*, T*, long, int, float, float,
                              unsigned long long, hipStream_t);
+void launch_flash_received(const __hip_bfloat16*, const __hip_bfloat16*, const int*, const float*,
+                           const float*, float*, int, int, int, float, int, long, long,
+                           hipStream_t);
 void dkv_prof_fetch(unsigned long long*);
 void fwd_prof_fetch(unsigned long long*);
 template <typename T>
@@ -864,6 +867,43 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor Q, at::Tensor K, at::Tensor V,
   return {O, lse};
 }
 
+// Attention received R[b, h, j] = sum_i P[b, h, i, j] from the forward's lse
+// (flash_received_kernel): fp32 (B, H, L), every element written
+at::Tensor flash_attn_received(at::Tensor Q, at::Tensor K, at::Tensor lse, int64_t H,
+                               c10::optional<at::Tensor> valid,
+                               c10::optional<at::Tensor> bias, double scale, bool causal) {
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16 && K.scalar_type() == at::kBFloat16,
+              "flash attention is bf16");
+  const int B = Q.size(0), L = Q.size(1);
+  const long ldq = fa_ld(Q, L);
+  const long ldkv = fa_ld(K, L);
+  TORCH_CHECK(K.device() == Q.device() && K.size(0) == B && K.size(1) == L &&
+                  K.size(2) == Q.size(2),
+              "Q and K must have the same shape and device");
+  TORCH_CHECK(Q.size(2) == H * 64, "head_dim must be 64");
+  TORCH_CHECK(L % 64 == 0, "L must be a multiple of 64");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == Q.device() && lse.dim() == 3 && lse.size(0) == B &&
+                  lse.size(1) == H && lse.size(2) == L,
+              "lse must be a contiguous fp32 (B, H, L) tensor on Q's device");
+  if (valid.has_value())
+    TORCH_CHECK(valid->device() == Q.device() && valid->numel() == B,
+                "valid must hold B lengths on Q's device");
+  const float* bptr = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+                bias->device() == Q.device());
+    TORCH_CHECK(bias->numel() == H * (long)L * L, "bias must be (H, L, L)");
+    bptr = bias->data_ptr<float>();
+  }
+  auto R = at::empty({B, H, L}, Q.options().dtype(at::kFloat));
+  if (R.numel() == 0) return R;
+  launch_flash_received(ptr<bf16_t>(Q), ptr<bf16_t>(K), opt_valid_ptr(valid), bptr,
+                        lse.data_ptr<float>(), R.data_ptr<float>(), B, H, L, (float)scale,
+                        causal ? 1 : 0, ldq, ldkv, cur_stream());
+  return R;
+}
+
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor dO, at::Tensor Q, at::Tensor K, at::Tensor V,
                                        at::Tensor O, at::Tensor lse, int64_t H,
                                        c10::optional<at::Tensor> valid,
@@ -1377,6 +1417,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_wgrad", &rmsnorm_wgrad, pybind11::arg("dy"), pybind11::arg("x"),
         pybind11::arg("rstd"), pybind11::arg("out") = pybind11::none());
   m.def("flash_attn_fwd", &flash_attn_fwd);
+  m.def("flash_attn_received", &flash_attn_received);
   m.def("flash_attn_bwd", &flash_attn_bwd, pybind11::arg("dO"), pybind11::arg("Q"),
         pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("O"), pybind11::arg("lse"),
         pybind11::arg("H"), pybind11::arg("valid"), pybind11::arg("bias"),

@@ -1127,6 +1127,142 @@ __global__ __launch_bounds__(256) void flash_dkv_kernel(
 #undef SEG_MARK
 }
 
+// ---------------------------------------------------------------------------
+// Attention received: R[b, h, j] = sum_i P[b, h, i, j], the column sums of
+// the pre-dropout probabilities (line-level localization scores a key token
+// by the total attention it receives). P is rebuilt from K, Q, bias and the
+// forward's lse exactly as the dK/dV pass rebuilds it, so no (L, L) buffer,
+// V or dO is touched. Masking is the family's: keys >= valid[b] (and, with
+// causal, keys > i) get P = 0. Padded QUERY rows i >= valid[b] are summed as
+// well — the materialised path and the reference mask keys only, and the
+// forward writes a real lse for those rows.
+//
+// One block owns a 64-key tile of one (b, h) and loops over 32-row query
+// strips on dkv's 2 (32-key halves) x 2 (strip interleave) wave grid. Each
+// lane keeps 8 fp32 column partials; the epilogue folds the 16 query lanes
+// with shfl_xor, the two interleaved waves through LDS in a fixed order, and
+// stores every one of the tile's 64 floats from exactly one lane: no atomics,
+// so results are bit-reproducible, and R may come from an uninitialised
+// allocation (tiles and keys past valid[b] store exact 0).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void flash_received_kernel(
+    const bf16* __restrict__ Q, const bf16* __restrict__ K,
+    const int* __restrict__ valid, const float* __restrict__ bias,
+    const float* __restrict__ lse, float* __restrict__ R, int B, int H, int L,
+    float scale, int causal, long ldq, long ldkv) {
+  // LDS map: K nat 8K (swizzled) | 64 fp32 wave-pair reduction slots
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* k_lds = smem;
+  float* red = reinterpret_cast<float*>(smem + TK * 128);
+
+  const int lid = blockIdx.y * gridDim.x + blockIdx.x;  // XCD-affine (see fwd)
+  const int S = gridDim.x * H;
+  const int b = lid / S;
+  const int h = (lid % S) / gridDim.x;
+  const int kv0 = ((lid % S) % gridDim.x) * TK;
+  const int bh = b * H + h;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x >> 6;
+  const int wk = wid >> 1;   // key half: keys wk*32 .. wk*32+31
+  const int wq = wid & 1;    // q interleave
+  const int key_off = wk * 32;
+  const int vl = valid ? valid[b] : L;
+
+  {  // stage the K tile (natural layout, swizzled); keys >= vl zero-filled
+    const int row = threadIdx.x >> 3;
+    const int off = (threadIdx.x & 7) * 16;
+#pragma unroll
+    for (int rr = 0; rr < TK; rr += 32) {
+      const int key = kv0 + row + rr;
+      uint4v kv = {};
+      if (key < vl)
+        kv = *reinterpret_cast<const uint4v*>(
+            K + ((long)b * L + key) * ldkv + (long)h * 64 + off / 2);
+      *reinterpret_cast<uint4v*>(k_lds + fa_swz(row + rr, off)) = kv;
+    }
+  }
+  __syncthreads();
+
+  // [fk][i]: key = key_off + fk*16 + (lane>>4)*4 + i, partial over this
+  // lane's query columns
+  float acc[2][4] = {};
+  if (kv0 < vl) {
+    const int q_begin = causal ? kv0 : 0;  // kv0 is a multiple of 32
+    const int nstrips = (L - q_begin + TQW - 1) / TQW;
+    for (int strip = wq; strip < nstrips; strip += 2) {
+      const int qw = q_begin + strip * TQW;
+      bf16x8 q_frag[2][2];
+      float lse_w[2];
+#pragma unroll
+      for (int fq = 0; fq < 2; ++fq) {
+        const int qrow = qw + fq * 16 + (lane & 15);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int d = ks * 32 + (lane >> 4) * 8;
+          if (qrow < L)
+            q_frag[fq][ks] = *reinterpret_cast<const bf16x8*>(
+                Q + ((long)b * L + qrow) * ldq + (long)h * 64 + d);
+          else
+            q_frag[fq][ks] = bf16x8{};
+        }
+        lse_w[fq] = (qrow < L) ? lse[(long)bh * L + qrow] : 0.f;
+      }
+      float p[2][2][4];
+      recompute_pT32(k_lds, q_frag, bias, lse_w, lane, h, L, qw, kv0, key_off,
+                     vl, scale, causal, p);
+#pragma unroll
+      for (int fk = 0; fk < 2; ++fk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[fk][i] += p[fk][0][i] + p[fk][1][i];
+    }
+  }
+
+  // fold the 16 query lanes (lane & 15) of each key group
+#pragma unroll
+  for (int fk = 0; fk < 2; ++fk)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float a = acc[fk][i];
+      a += __shfl_xor(a, 1);
+      a += __shfl_xor(a, 2);
+      a += __shfl_xor(a, 4);
+      a += __shfl_xor(a, 8);
+      acc[fk][i] = a;
+    }
+  // wave pair (wq 0/1) of a key half: wq=1 parks its sums, wq=0 adds them
+  // (always wq0 + wq1) and stores its half's 32 floats, 4 per lane
+  const bool owner = (lane & 15) == 0;
+  if (wq == 1 && owner) {
+#pragma unroll
+    for (int fk = 0; fk < 2; ++fk)
+      *reinterpret_cast<f32x4*>(red + key_off + fk * 16 + (lane >> 4) * 4) =
+          f32x4{acc[fk][0], acc[fk][1], acc[fk][2], acc[fk][3]};
+  }
+  __syncthreads();
+  if (wq == 0 && owner) {
+#pragma unroll
+    for (int fk = 0; fk < 2; ++fk) {
+      const int key_loc = key_off + fk * 16 + (lane >> 4) * 4;  // kv0 + 63 < L
+      const f32x4 other = *reinterpret_cast<const f32x4*>(red + key_loc);
+      *reinterpret_cast<f32x4*>(R + (long)bh * L + kv0 + key_loc) =
+          f32x4{acc[fk][0] + other[0], acc[fk][1] + other[1],
+                acc[fk][2] + other[2], acc[fk][3] + other[3]};
+    }
+  }
+}
+
+void launch_flash_received(const bf16* Q, const bf16* K, const int* valid,
+                           const float* bias, const float* lse, float* R,
+                           int B, int H, int L, float scale, int causal,
+                           long ldq, long ldkv, hipStream_t stream) {
+  // L % 64 == 0 (checked by the binding): every tile is whole, so neither
+  // the bias reads nor the R stores need a key < L guard
+  const dim3 grid(L / TK, B * H);
+  const size_t lds = TK * 128 + TK * sizeof(float);
+  hipLaunchKernelGGL(flash_received_kernel, grid, dim3(256), lds, stream, Q, K,
+                     valid, bias, lse, R, B, H, L, scale, causal, ldq, ldkv);
+}
+
 void fwd_prof_fetch(unsigned long long* out) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dfa_fwd_prof),
                             8 * sizeof(unsigned long long));

@@ -67,22 +67,29 @@ class Model(nn.Module):
         labels: Optional[torch.Tensor] = None,
         graphs=None,
         output_attentions: bool = False,
+        attention_received: bool = False,
     ):
+        """`attention_received` mirrors `output_attentions`, but the extra
+        return value is the per-layer list of (B, H, L) fp32 attention each
+        key token receives (the column sums of the probabilities) — on
+        flash-usable inputs computed by the fused kernels with no (L, L)
+        tensor. An inference output: it carries no gradient."""
         attention_mask = input_ids.ne(1)
         if self.flowgnn_encoder is not None and graphs is not None:
             flowgnn_embed = self.flowgnn_encoder(graphs, {})
         else:
             flowgnn_embed = None
         hidden, attentions = self.encoder(
-            input_ids, attention_mask=attention_mask, output_attentions=output_attentions
+            input_ids, attention_mask=attention_mask, output_attentions=output_attentions,
+            attention_received=attention_received,
         )
         logits = self.classifier(hidden, flowgnn_embed)
         prob = torch.softmax(logits.float(), dim=-1)
         if labels is not None:
             loss = torch.nn.functional.cross_entropy(logits.float(), labels)
-            if output_attentions:
+            if output_attentions or attention_received:
                 return loss, prob, attentions
             return loss, prob
-        if output_attentions:
+        if output_attentions or attention_received:
             return prob, attentions
         return prob

@@ -115,9 +115,12 @@ class RobertaSelfAttention(nn.Module):
         self.dropout_p = cfg.attention_probs_dropout_prob
         self.dropout = nn.Dropout(cfg.attention_probs_dropout_prob)  # CPU path
 
-    def forward(self, x, valid: Optional[torch.Tensor], output_attentions: bool = False):
+    def forward(self, x, valid: Optional[torch.Tensor], output_attentions: bool = False,
+                attention_received: bool = False):
         from ..ops.transformer import fused_qkv
 
+        if attention_received:
+            return self._forward_received(x, valid)
         B, L, D = x.shape
         H, d = self.num_heads, self.head_dim
         p = self.dropout_p if self.training else 0.0
@@ -150,6 +153,34 @@ class RobertaSelfAttention(nn.Module):
         out = ctx.transpose(1, 2).reshape(B, L, D)
         return (out, probs) if output_attentions else (out, None)
 
+    def _forward_received(self, x, valid):
+        """(out, R) with R[b, h, j] = sum_i probs[b, h, i, j], fp32 (B, H, L):
+        the attention each key token receives (line-level localization).
+        Flash-usable inputs stay on the fused kernels and never build the
+        (B, H, L, L) probabilities; everything else sums the materialised
+        ones. An inference output: no gradient, no dropout."""
+        from ..ops.transformer import (
+            flash_attention_received,
+            flash_attention_received_qkv,
+            fused_qkv,
+        )
+
+        B, L, D = x.shape
+        H, d = self.num_heads, self.head_dim
+        scale = 1.0 / math.sqrt(d)
+        if d == 64 and flash_usable(x, L):
+            with torch.no_grad():
+                qkv = fused_qkv(x, self.query.weight, self.key.weight, self.value.weight,
+                                self.query.bias, self.key.bias, self.value.bias)
+                if qkv is not None:
+                    return flash_attention_received_qkv(qkv, H, valid=valid, scale=scale)
+                q = fused_linear(x, self.query.weight, self.query.bias)
+                k = fused_linear(x, self.key.weight, self.key.bias)
+                v = fused_linear(x, self.value.weight, self.value.bias)
+                return flash_attention_received(q, k, v, H, valid=valid, scale=scale)
+        out, probs = self.forward(x, valid, output_attentions=True)
+        return out, probs.float().sum(dim=-2)
+
 
 class RobertaSelfOutput(nn.Module):
     def __init__(self, cfg):
@@ -171,8 +202,8 @@ class RobertaAttention(nn.Module):
         self.self = RobertaSelfAttention(cfg)
         self.output = RobertaSelfOutput(cfg)
 
-    def forward(self, x, valid, output_attentions=False):
-        out, probs = self.self(x, valid, output_attentions)
+    def forward(self, x, valid, output_attentions=False, attention_received=False):
+        out, probs = self.self(x, valid, output_attentions, attention_received)
         return self.output(out, x), probs
 
 
@@ -207,8 +238,8 @@ class RobertaLayer(nn.Module):
         self.intermediate = RobertaIntermediate(cfg)
         self.output = RobertaOutput(cfg)
 
-    def forward(self, x, valid, output_attentions=False):
-        attn_out, probs = self.attention(x, valid, output_attentions)
+    def forward(self, x, valid, output_attentions=False, attention_received=False):
+        attn_out, probs = self.attention(x, valid, output_attentions, attention_received)
         return self.output(self.intermediate(attn_out), attn_out), probs
 
 
@@ -217,12 +248,22 @@ class RobertaEncoder(nn.Module):
         super().__init__()
         self.layer = nn.ModuleList([RobertaLayer(cfg) for _ in range(cfg.num_hidden_layers)])
 
-    def forward(self, x, valid, output_attentions=False):
-        all_probs = [] if output_attentions else None
-        for lyr in self.layer:
-            x, probs = lyr(x, valid, output_attentions)
-            if output_attentions:
+    def forward(self, x, valid, output_attentions=False, attention_received=False,
+                stop_after: Optional[int] = None):
+        """`attention_received` returns, in place of the per-layer
+        probabilities, the per-layer (B, H, L) fp32 attention each key
+        receives. `stop_after` = index of the last layer to run (None: all);
+        the returned hidden state is then that layer's output."""
+        if output_attentions and attention_received:
+            raise ValueError("output_attentions and attention_received are exclusive")
+        collect = output_attentions or attention_received
+        all_probs = [] if collect else None
+        for i, lyr in enumerate(self.layer):
+            x, probs = lyr(x, valid, output_attentions, attention_received)
+            if collect:
                 all_probs.append(probs)
+            if stop_after is not None and i >= stop_after:
+                break
         return x, all_probs
 
 
@@ -233,7 +274,10 @@ class RobertaModel(nn.Module):
         self.embeddings = RobertaEmbeddings(cfg)
         self.encoder = RobertaEncoder(cfg)
 
-    def forward(self, input_ids, attention_mask=None, output_attentions=False):
+    def forward(self, input_ids, attention_mask=None, output_attentions=False,
+                attention_received=False, stop_after: Optional[int] = None):
+        if output_attentions and attention_received:
+            raise ValueError("output_attentions and attention_received are exclusive")
         if attention_mask is None:
             attention_mask = input_ids.ne(self.config.pad_token_id)
         valid = attention_mask.sum(dim=1).to(torch.int32)
@@ -243,7 +287,8 @@ class RobertaModel(nn.Module):
         # flash kernels take bf16 activations against fp32 master weights)
         if x.is_cuda and torch.is_autocast_enabled():
             x = x.to(torch.bfloat16)
-        hidden, all_probs = self.encoder(x, valid, output_attentions)
+        hidden, all_probs = self.encoder(x, valid, output_attentions, attention_received,
+                                         stop_after)
         return hidden, all_probs
 
 

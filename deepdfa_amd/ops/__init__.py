@@ -1,5 +1,10 @@
 from ._ext import has_ext, load_ext
 from .flowgnn import attn_pool, embed4, gru_cell, segment_max, spmm_sum
+from .transformer import (
+    attention_received,
+    flash_attention_received,
+    flash_attention_received_qkv,
+)
 
 __all__ = [
     "has_ext",
@@ -9,4 +14,7 @@ __all__ = [
     "gru_cell",
     "attn_pool",
     "segment_max",
+    "attention_received",
+    "flash_attention_received",
+    "flash_attention_received_qkv",
 ]

@@ -656,6 +656,78 @@ def flash_attention_qkv(qkv, num_heads, valid=None, bias=None, scale=1.0,
                                     dropout_p, bias_accum)
 
 
+def attention_received(q, k, num_heads, lse, valid=None, bias=None, scale=1.0,
+                       causal=False):
+    """R[b, h, j] = sum_i P[b, h, i, j], fp32 (B, H, L): the total attention
+    each key token receives, with P = softmax_j(scale * q_i.k_j + bias[h, j, i])
+    pre-dropout. Keys >= valid[b] (and, with `causal`, keys > i) are masked;
+    padded query rows i >= valid[b] are summed like every other row, as the
+    materialised path and the reference do. `bias` is fp32 key-major
+    (H, Lk, Lq). Inference output: no gradient flows through it.
+
+    On the GPU with bf16 head_dim-64 inputs and L % 64 == 0 this is
+    flash_received_kernel, which rebuilds P from q, k and the forward's
+    `lse`. Anything else computes the same quantity materialised in fp32;
+    `lse` is then ignored and may be None."""
+    B, L, D = q.shape
+    H = num_heads
+    with torch.no_grad():
+        if (D == H * 64 and k.dtype == q.dtype and k.is_cuda
+                and flash_usable(q, L, k.shape[1])):
+            if lse is None:
+                raise ValueError("attention_received needs the forward's lse on the kernel path")
+            ext = load_ext(required=True)
+            return ext.flash_attn_received(q, k, lse, H, valid, bias, scale, causal)
+        d = D // H
+        qh = q.float().view(B, L, H, d).transpose(1, 2)
+        kh = k.float().view(B, k.shape[1], H, d).transpose(1, 2)
+        s = torch.matmul(qh, kh.transpose(-1, -2)) * scale
+        Lk = s.shape[-1]
+        if bias is not None:
+            s = s + bias.float().view(H, Lk, L).transpose(-1, -2)
+        ar = torch.arange(Lk, device=s.device)
+        if valid is not None:
+            s = s.masked_fill(ar.view(1, 1, 1, Lk) >= valid.view(-1, 1, 1, 1), float("-inf"))
+        if causal:
+            qi = torch.arange(L, device=s.device)
+            s = s.masked_fill((ar.view(1, Lk) > qi.view(L, 1)).view(1, 1, L, Lk), float("-inf"))
+        p = torch.nan_to_num(torch.softmax(s, dim=-1), nan=0.0)
+        return p.sum(dim=-2)
+
+
+def _no_grad_inputs(name, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise ValueError(
+            f"{name} is an inference output: call it under torch.no_grad() "
+            "or on inputs that do not require grad"
+        )
+
+
+def flash_attention_received(q, k, v, num_heads, valid=None, bias=None, scale=1.0,
+                             causal=False):
+    """(O, R): the flash forward's output (bit-identical to flash_attention at
+    dropout_p = 0 — it is the same kernel launch) and the attention each key
+    receives, computed from that forward's lse. Inference only: returns
+    tensors without grad and raises ValueError on inputs that would need one."""
+    _no_grad_inputs("flash_attention_received", q, k, v, bias)
+    ext = load_ext(required=True)
+    with torch.no_grad():
+        O, lse = ext.flash_attn_fwd(q, k, v, num_heads, valid, bias, scale, causal, 0.0, 0)
+        R = ext.flash_attn_received(q, k, lse, num_heads, valid, bias, scale, causal)
+    return O, R
+
+
+def flash_attention_received_qkv(qkv, num_heads, valid=None, bias=None, scale=1.0,
+                                 causal=False):
+    """flash_attention_received on the fused (B, L, 3D) projection: q/k/v are
+    strided views, no copies."""
+    _no_grad_inputs("flash_attention_received_qkv", qkv, bias)
+    D = qkv.shape[-1] // 3
+    with torch.no_grad():
+        q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        return flash_attention_received(q, k, v, num_heads, valid, bias, scale, causal)
+
+
 class _LMHeadCE(torch.autograd.Function):
     """K21: fused LM-head GEMM + cross-entropy over the 32100-token vocab
     (csrc/lmhead_ce.hip). Forward streams vocab tiles with online

@@ -3,7 +3,9 @@
 Parity target: reference LineVul/unixcoder/linevul_main.py (1779 lines) —
 the extended LineVul driver with the UniXcoder backbone plus:
   * line_level_localization (:955-1242): the full 5-method matrix —
-    attention (last-layer heads summed), input-x-gradient saliency,
+    attention (heads summed; last layer by default, --attention_layer 0
+    is the reference's first layer; batched on the fused kernels by
+    attention_line_scores_batched), input-x-gradient saliency,
     integrated gradients (lig), DeepLift rescale, and GradientShap — all
     captum-free own implementations over the embedding layer;
   * Effort@TopK% and Recall@TopK%LOC metrics (:886-944);
@@ -78,6 +80,39 @@ def attention_line_scores(model: Model, ids: torch.Tensor, token_lines: List[int
         if ln >= 0:
             scores[ln] = scores.get(ln, 0.0) + float(tok_score[j])
     return scores
+
+
+@torch.no_grad()
+def attention_line_scores_batched(model: Model, ids: torch.Tensor, token_lines: torch.Tensor,
+                                  layer: int = -1) -> torch.Tensor:
+    """Batched 'attention' localization: (B, n_lines) fp32 line scores for
+    `ids` (B, L) and `token_lines` (B, L; -1 for CLS/SEP/PAD as
+    encode_with_lines produces), n_lines = token_lines.max() + 1.
+
+    Runs the embeddings and encoder layers 0..`layer` only, asking for the
+    attention each key token receives instead of the probabilities: on the
+    GPU (bf16 autocast, as the test/eval loop) that is the fused QKV GEMM,
+    flash attention and flash_received_kernel, with no (B, H, L, L) tensor.
+    Heads are summed, then tokens are summed into their lines on the device.
+    `layer` = -1 is the last layer, as attention_line_scores; the reference
+    scores layer 0 (LineVul/unixcoder/linevul_main.py:1156)."""
+    model.eval()
+    n_layers = len(model.encoder.encoder.layer)
+    if not -n_layers <= layer < n_layers:
+        raise ValueError(f"attention layer {layer} out of range for {n_layers} layers")
+    layer = layer % n_layers
+    token_lines = token_lines.to(ids.device)
+    with torch.autocast(device_type="cuda", dtype=torch.bfloat16, enabled=ids.is_cuda):
+        _hidden, received = model.encoder(ids, attention_mask=ids.ne(1),
+                                          attention_received=True, stop_after=layer)
+    tok = received[layer].float().sum(dim=1)  # (B, L): heads summed
+    n_lines = int(token_lines.max()) + 1 if token_lines.numel() else 0
+    n_lines = max(n_lines, 0)
+    # special/pad tokens (line -1) land in one extra column that is dropped
+    out = torch.zeros(ids.shape[0], n_lines + 1, dtype=torch.float32, device=ids.device)
+    index = torch.where(token_lines < 0, torch.full_like(token_lines, n_lines), token_lines)
+    out.scatter_add_(1, index, tok)
+    return out[:, :n_lines]
 
 
 def saliency_line_scores(model: Model, ids: torch.Tensor, token_lines: List[int]) -> Dict[int, float]:
@@ -326,6 +361,11 @@ def main(argv=None):
     p.add_argument("--reasoning_method", default="attention",
                    choices=["attention", "saliency", "gradient", "lig", "ig",
                             "deeplift", "shap", "gradientshap", "deeplift_shap"])
+    p.add_argument("--attention_layer", type=int, default=-1,
+                   help="encoder layer whose attention the 'attention' method scores "
+                        "(-1 = last, this port's default). The reference scores the "
+                        "first layer, 0: attentions[0][0] at "
+                        "LineVul/unixcoder/linevul_main.py:1156")
     p.add_argument("--top_k_constant", type=int, default=10)
     p.add_argument("--effort_at_top_k", type=float, default=0.2)
     p.add_argument("--top_k_recall_loc", type=float, default=0.01)
@@ -382,9 +422,25 @@ def main(argv=None):
         export_codet5_dataset(datasets["test"], os.path.join(args.output_dir, "test.jsonl"))
     if args.do_local_explanation:
         line_results = []
-        for row in list(datasets["test"].df.itertuples())[:50]:
-            if not row.vul:
-                continue
+        rows = [row for row in list(datasets["test"].df.itertuples())[:50] if row.vul]
+        if args.reasoning_method == "attention":
+            # batched: encode every selected function, score eval_batch_size
+            # of them per encoder pass
+            enc = [encode_with_lines(tokenizer, row.func, args.block_size) for row in rows]
+            bs = max(1, args.eval_batch_size)
+            for c0 in range(0, len(rows), bs):
+                ids_b = torch.tensor([e[0] for e in enc[c0:c0 + bs]], dtype=torch.long,
+                                     device=device)
+                lines_b = torch.tensor([e[1] for e in enc[c0:c0 + bs]], dtype=torch.long,
+                                       device=device)
+                got = attention_line_scores_batched(model, ids_b, lines_b,
+                                                    args.attention_layer).cpu()
+                for row, sc in zip(rows[c0:c0 + bs], got):
+                    n_lines = len(row.func.split("\n"))
+                    vec = [float(sc[i]) if i < sc.shape[0] else 0.0 for i in range(n_lines)]
+                    line_results.append((vec, [min(2, n_lines - 1)]))
+            rows = []
+        for row in rows:
             ids, tok_lines = encode_with_lines(tokenizer, row.func, args.block_size)
             ids_t = torch.tensor(ids, dtype=torch.long, device=device)
             scores = line_level_localization(model, ids_t, tok_lines, args.reasoning_method)
