@@ -42,7 +42,12 @@ void launch_spmm_sum_strided(const int*, const int*, const T*, T*, int, int, lon
 void launch_gemm_bias2(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                        const __hip_bfloat16*, const __hip_bfloat16*, long,
                        const __hip_bfloat16*, long, __hip_bfloat16*, int, int, int, int,
-                       hipStream_t);
+                       hipStream_t, const int* = nullptr, const int* = nullptr, long = 0,
+                       __hip_bfloat16* = nullptr);
+bool launch_gates_gemm(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                       const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                       const __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*,
+                       __hip_bfloat16*, int, int, hipStream_t);
 void launch_gemm_bias(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                       const __hip_bfloat16*, const __hip_bfloat16*, __hip_bfloat16*, int, int,
                       int, int, hipStream_t);
@@ -378,7 +383,8 @@ void launch_pack_gru_weights(const float*, const float*, const float*, const flo
 void launch_gemm_gru(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                      const __hip_bfloat16*, const __hip_bfloat16*, __hip_bfloat16*,
                      __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*, __hip_bfloat16*,
-                     int, int, int, int, hipStream_t);
+                     int, int, int, int, hipStream_t, const int* = nullptr,
+                     const int* = nullptr, __hip_bfloat16* = nullptr);
 
 // one-launch refresh of every derived GGNN weight buffer (bf16 casts,
 // Wcat/WcatT block matrix, merged bias) — see ops/flowgnn.py cache
@@ -402,7 +408,7 @@ void pack_gru_weights(at::Tensor W_e, at::Tensor b_e, at::Tensor W_ih, at::Tenso
 
 std::vector<at::Tensor> ggnn_fused_fwd(at::Tensor indptr, at::Tensor indices, at::Tensor x,
                                        at::Tensor W_e, at::Tensor b_e, at::Tensor Wcat_perm,
-                                       at::Tensor b_perm, long n_steps) {
+                                       at::Tensor b_perm, long n_steps, bool fuse) {
   CHECK_GPU(x);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fused GGNN path is bf16");
   const long N = x.size(0);
@@ -429,14 +435,19 @@ std::vector<at::Tensor> ggnn_fused_fwd(at::Tensor indptr, at::Tensor indices, at
     launch_gemm_bias(h, nullptr, ptr<bf16_t>(W_e), ptr<bf16_t>(b_e), nullptr, mptr<bf16_t>(wh),
                      N, H, H, H, stream);
     bf16_t* m = mptr<bf16_t>(M) + s * NH;
-    launch_spmm_sum<bf16_t>(indptr.data_ptr<int>(), indices.data_ptr<int>(), ptr<bf16_t>(wh), m,
-                            N, H, stream);
+    // fuse: M[s] = spmm_sum(wh) is formed in gemm_gru's A staging (and
+    // stored from there); otherwise by its own launch
+    if (!fuse)
+      launch_spmm_sum<bf16_t>(indptr.data_ptr<int>(), indices.data_ptr<int>(), ptr<bf16_t>(wh),
+                              m, N, H, stream);
     // fused gate GEMM + GRU cell (gate-interleaved Wcat layout): replaces
     // the gicat GEMM + separate gru_gates2_fwd, with fp32 pre-activations
-    launch_gemm_gru(m, h, ptr<bf16_t>(Wcat_perm), ptr<bf16_t>(b_perm), h,
-                    mptr<bf16_t>(HH) + (s + 1) * NH, mptr<bf16_t>(R) + s * NH,
+    launch_gemm_gru(fuse ? ptr<bf16_t>(wh) : m, h, ptr<bf16_t>(Wcat_perm), ptr<bf16_t>(b_perm),
+                    h, mptr<bf16_t>(HH) + (s + 1) * NH, mptr<bf16_t>(R) + s * NH,
                     mptr<bf16_t>(Z) + s * NH, mptr<bf16_t>(Nn) + s * NH,
-                    mptr<bf16_t>(HN) + s * NH, N, 2 * H, H, H, stream);
+                    mptr<bf16_t>(HN) + s * NH, N, 2 * H, H, H, stream,
+                    fuse ? indptr.data_ptr<int>() : nullptr,
+                    fuse ? indices.data_ptr<int>() : nullptr, fuse ? m : nullptr);
   }
   auto h_final = HH.select(0, S);
   return {h_final, HH, M, R, Z, Nn, HN};
@@ -449,7 +460,8 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
                                        at::Tensor HN, long n_steps,
                                        c10::optional<at::Tensor> out_we,
                                        c10::optional<at::Tensor> out_be,
-                                       c10::optional<std::vector<at::Tensor>> gru_outs) {
+                                       c10::optional<std::vector<at::Tensor>> gru_outs,
+                                       bool fuse) {
   const long N = x.size(0);
   const long H = x.size(1);
   const long S = n_steps;
@@ -463,29 +475,51 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
   // custom split-K wgrad kernel replaces; see csrc/wgrad.hip header)
   auto Ggicat = at::empty({S, N, 4 * H}, opts);
   auto Gwh = at::empty({S, N, H}, opts);
-  auto grad_h = grad_out.contiguous().clone();
+  // grad_out is only read: step S-1 takes it as its incoming grad, and every
+  // step writes the grad of its h_in into the loop's own buffer
+  auto go = grad_out.contiguous();
+  auto grad_h = S > 0 ? at::empty({N, H}, opts) : go.clone();
   auto grad_hd = at::empty({N, H}, opts);
   auto grad_A = at::empty({N, 2 * H}, opts);
   for (long s = S - 1; s >= 0; --s) {
     const bf16_t* h_in = ptr<bf16_t>(HH) + s * NH;
+    const bf16_t* g_in = (s == S - 1) ? ptr<bf16_t>(go) : ptr<bf16_t>(grad_h);
     auto ggic = Ggicat.select(0, s);
     auto gwh = Gwh.select(0, s);
-    launch_gru_gates2_bwd<bf16_t>(ptr<bf16_t>(grad_h), h_in, ptr<bf16_t>(R) + s * NH,
-                                  ptr<bf16_t>(Z) + s * NH, ptr<bf16_t>(Nn) + s * NH,
-                                  ptr<bf16_t>(HN) + s * NH, mptr<bf16_t>(ggic),
-                                  mptr<bf16_t>(grad_hd), NH, H, stream);
-    // grad_A = ggic @ Wcat : (N, 2H); left half = grad_m, right = gh-path
-    launch_gemm_bias(ptr<bf16_t>(ggic), nullptr, ptr<bf16_t>(WcatT), nullptr, nullptr,
-                     mptr<bf16_t>(grad_A), N, 4 * H, 4 * H, 2 * H, stream);
-    // grad_m read STRIDED out of grad_A's left half (no contiguous copy)
-    launch_spmm_sum_strided<bf16_t>(t_indptr.data_ptr<int>(), t_indices.data_ptr<int>(),
-                                    ptr<bf16_t>(grad_A), mptr<bf16_t>(gwh), N, H,
-                                    2 * H, stream);
+    // grad_A = ggic @ Wcat : (N, 2H); left half = grad_m, right = gh-path.
+    // fuse: the gate backward is the GEMM's prologue (one launch) where the
+    // tile fits; otherwise gru_gates2_bwd writes ggic and the GEMM reads it
+    if (!fuse ||
+        !launch_gates_gemm(g_in, h_in, ptr<bf16_t>(R) + s * NH, ptr<bf16_t>(Z) + s * NH,
+                           ptr<bf16_t>(Nn) + s * NH, ptr<bf16_t>(HN) + s * NH,
+                           ptr<bf16_t>(WcatT), mptr<bf16_t>(ggic), mptr<bf16_t>(grad_hd),
+                           mptr<bf16_t>(grad_A), N, H, stream)) {
+      launch_gru_gates2_bwd<bf16_t>(g_in, h_in, ptr<bf16_t>(R) + s * NH,
+                                    ptr<bf16_t>(Z) + s * NH, ptr<bf16_t>(Nn) + s * NH,
+                                    ptr<bf16_t>(HN) + s * NH, mptr<bf16_t>(ggic),
+                                    mptr<bf16_t>(grad_hd), NH, H, stream);
+      launch_gemm_bias(ptr<bf16_t>(ggic), nullptr, ptr<bf16_t>(WcatT), nullptr, nullptr,
+                       mptr<bf16_t>(grad_A), N, 4 * H, 4 * H, 2 * H, stream);
+    }
     // grad wrt h_in = (grad_wh @ W_e) + direct z-path + gh-path, the two
-    // additions fused into the GEMM epilogue as strided addends
-    launch_gemm_bias2(ptr<bf16_t>(gwh), nullptr, ptr<bf16_t>(W_eT), nullptr,
-                      ptr<bf16_t>(grad_hd), H, ptr<bf16_t>(grad_A) + H, 2 * H,
-                      mptr<bf16_t>(grad_h), N, H, H, H, stream);
+    // additions fused into the GEMM epilogue as strided addends. grad_wh =
+    // Gwh[s] is the CSC segment sum of grad_m, read STRIDED out of grad_A's
+    // left half (no contiguous copy). fuse: summed in the GEMM's A staging
+    // (and stored from there); otherwise by its own launch
+    if (fuse) {
+      launch_gemm_bias2(ptr<bf16_t>(grad_A), nullptr, ptr<bf16_t>(W_eT), nullptr,
+                        ptr<bf16_t>(grad_hd), H, ptr<bf16_t>(grad_A) + H, 2 * H,
+                        mptr<bf16_t>(grad_h), N, H, H, H, stream,
+                        t_indptr.data_ptr<int>(), t_indices.data_ptr<int>(), 2 * H,
+                        mptr<bf16_t>(gwh));
+    } else {
+      launch_spmm_sum_strided<bf16_t>(t_indptr.data_ptr<int>(), t_indices.data_ptr<int>(),
+                                      ptr<bf16_t>(grad_A), mptr<bf16_t>(gwh), N, H,
+                                      2 * H, stream);
+      launch_gemm_bias2(ptr<bf16_t>(gwh), nullptr, ptr<bf16_t>(W_eT), nullptr,
+                        ptr<bf16_t>(grad_hd), H, ptr<bf16_t>(grad_A) + H, 2 * H,
+                        mptr<bf16_t>(grad_h), N, H, H, H, stream);
+    }
   }
   // batched weight/bias grads over all steps (K = S*N)
   auto A_g = Ggicat.view({S * N, 4 * H});
@@ -1368,7 +1402,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_gates2_fwd", &gru_gates2_fwd);
   m.def("gru_gates2_bwd", &gru_gates2_bwd);
   m.def("colsum", &colsum, pybind11::arg("x"), pybind11::arg("out") = pybind11::none());
-  m.def("ggnn_fused_fwd", &ggnn_fused_fwd);
+  m.def("ggnn_fused_fwd", &ggnn_fused_fwd, pybind11::arg("indptr"), pybind11::arg("indices"),
+        pybind11::arg("x"), pybind11::arg("W_e"), pybind11::arg("b_e"),
+        pybind11::arg("Wcat_perm"), pybind11::arg("b_perm"), pybind11::arg("n_steps"),
+        pybind11::arg("fuse") = true);
   m.def("pack_gru_weights", &pack_gru_weights);
   m.def("bce_logits_fwd", [](at::Tensor logits, at::Tensor labels,
                              c10::optional<at::Tensor> weight,
@@ -1617,5 +1654,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("HN"), pybind11::arg("n_steps"),
         pybind11::arg("out_we") = pybind11::none(),
         pybind11::arg("out_be") = pybind11::none(),
-        pybind11::arg("gru_outs") = pybind11::none());
+        pybind11::arg("gru_outs") = pybind11::none(), pybind11::arg("fuse") = true);
 }

@@ -18,6 +18,8 @@
 #include <algorithm>
 using std::min;
 
+#include "gru_gate_bwd.h"
+
 #define WAVE 64
 
 // ---------------------------------------------------------------------------
@@ -249,17 +251,12 @@ __global__ void gru_gates2_bwd_kernel(const T* __restrict__ grad_h_new,
     const float r = to_f(r_i[i]), z = to_f(z_i[i]), n = to_f(n_i[i]);
     const float hn = to_f(hn_i[i]);
     const float hv = to_f(h[i]);
-    const float dn = go * (1.f - z);
-    const float dz = go * (hv - n);
-    const float dpn = dn * (1.f - n * n);
-    const float dr = dpn * hn;
-    const float dpr = dr * r * (1.f - r);
-    const float dpz = dz * z * (1.f - z);
-    grad_gicat[b] = from_f<T>(dpr);
-    grad_gicat[b + H] = from_f<T>(dpz);
-    grad_gicat[b + 2 * H] = from_f<T>(dpn);
-    grad_gicat[b + 3 * H] = from_f<T>(dpn * r);
-    grad_h[i] = from_f<T>(go * z);
+    const GruGate2Grad d = gru_gate2_bwd_elem(go, hv, r, z, n, hn);
+    grad_gicat[b] = from_f<T>(d.dpr);
+    grad_gicat[b + H] = from_f<T>(d.dpz);
+    grad_gicat[b + 2 * H] = from_f<T>(d.dpn);
+    grad_gicat[b + 3 * H] = from_f<T>(d.dpnr);
+    grad_h[i] = from_f<T>(d.ghd);
   }
 }
 

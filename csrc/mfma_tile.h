@@ -137,6 +137,69 @@ __device__ __forceinline__ void tile_regs_store(char* lds, int tid,
     *reinterpret_cast<uint4v*>(lds + tile_swz(srow + p * 32, soff)) = r[p];
 }
 
+// ---- gathered A chunk: one 16-B chunk of a CSR segment sum ----
+// The A1 half of a register-staged GEMM can be a segment sum over a CSR
+// graph instead of a stored matrix: A1'[v] = sum_{e in [indptr[v],
+// indptr[v+1])} A1[indices[e]]. The sum starts at 0.f, adds in edge order in
+// fp32 and rounds to bf16 once, which is spmm_sum_kernel's arithmetic, so
+// the staged chunk holds the bits that kernel would have written
+// (flowgnn_kernels.hip).
+struct TileGather {
+  const int* indptr;   // (N + 1)
+  const int* indices;  // source row per edge
+  long lda;            // row stride of the gathered matrix, elements
+  bf16* out;           // (N, K1) copy of the staged sums, or nullptr
+};
+
+union tile_pack8 {
+  uint4v v;
+  bf16 e[8];
+};
+
+// The gather is split like every other staged load of the pipeline: the
+// rows of a segment's first GPF edges (their indices are fetched once,
+// before the K loop) are requested with the slice's other global loads,
+// ahead of the current slice's MFMAs, and summed here, after them. Edges
+// past those (on the synthetic training graphs 18% / 35% of the nodes have
+// more than 2 in- / out-edges, 0.1% / 0.7% more than 4) are walked here,
+// their latency exposed, two in flight per trip; the second index of an
+// odd tail is clamped (a repeated, in-bounds load) and its add skipped.
+// src points at this chunk's column of row 0.
+template <int GPF>
+__device__ __forceinline__ uint4v tile_gather_finish(const uint4v raw[GPF],
+                                                     const bf16* __restrict__ src,
+                                                     long lda,
+                                                     const int* __restrict__ indices,
+                                                     int e0, int e1) {
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  tile_pack8 v0, v1;
+#pragma unroll
+  for (int q = 0; q < GPF; ++q) {
+    if (e0 + q < e1) {
+      v0.v = raw[q];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] += __bfloat162float(v0.e[j]);
+    }
+  }
+  for (int e = e0 + GPF; e < e1; e += 2) {
+    const bool two = e + 1 < e1;
+    const int i0 = indices[e];
+    const int i1 = indices[two ? e + 1 : e];
+    v0.v = *reinterpret_cast<const uint4v*>(src + (long)i0 * lda);
+    v1.v = *reinterpret_cast<const uint4v*>(src + (long)i1 * lda);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] += __bfloat162float(v0.e[j]);
+    if (two) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] += __bfloat162float(v1.e[j]);
+    }
+  }
+  tile_pack8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o.e[j] = __float2bfloat16(a[j]);
+  return o.v;
+}
+
 // ---- register-staged main loop (T14 double buffering), 2x2 waves ----
 // acc(BMT x 128 block tile at (r0, c0)) = [A1|A2](N, K) @ W(COL, K)^T, K
 // columns [0, K1) from A1 and [K1, K) from A2; rows >= N read as zero.
@@ -144,25 +207,67 @@ __device__ __forceinline__ void tile_regs_store(char* lds, int tid,
 // N x 128-ish GEMMs are HBM-latency-bound at ~1.4 blocks/CU;
 // single-buffered staging serialized load latency with the MFMA phase).
 // On return every wave is past the last barrier: smem may be reused.
-template <int BMT, bool CT>
+// GPF > 0 (GATHER): the A1 half is the segment sum (tile_gather_finish,
+// GPF edges prefetched per row) over A1's rows (row stride g.lda), which
+// index the whole matrix, not the block's rows; A2 and the K order of the
+// slices are unchanged,
+// so the accumulators see the sequence they would see reading the stored
+// sum. With g.out set, the staged chunks of rows < N are also stored there.
+template <int BMT, bool CT, int GPF = 0>
 __device__ __forceinline__ void tile_regstaged_gemm(
     f32x4 (&acc)[BMT / 32][4], char* smem, const bf16* __restrict__ A1,
     const bf16* __restrict__ A2, int K1, const bf16* __restrict__ W, int N,
-    int K, int COL, int r0, int c0) {
+    int K, int COL, int r0, int c0, const TileGather g = {}) {
   constexpr int NAR = BMT / 32;  // A rows per thread
+  constexpr bool GATHER = GPF > 0;
+  constexpr int NPF = GATHER ? GPF : 1;
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wm = tid >> 7;       // 2 row-waves of BMT/2 rows
   const int wn = (tid >> 6) & 1;  // 2 col-waves of 64 cols
   const int srow = tid >> 3;
   const int soff = (tid & 7) * 16;
-  auto load_regs = [&](int kk, uint4v ar[NAR], uint4v br[4]) {
+  // GATHER: this thread's rows' edge ranges and first GPF source rows
+  int ge0[NAR], ge1[NAR], gi[NAR][NPF];
+  if constexpr (GATHER) {
+#pragma unroll
+    for (int p = 0; p < NAR; ++p) {
+      const int gr = r0 + srow + p * 32;
+      ge0[p] = ge1[p] = 0;
+      if (gr < N) {
+        ge0[p] = g.indptr[gr];
+        ge1[p] = g.indptr[gr + 1];
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < NAR; ++p)
+#pragma unroll
+      for (int q = 0; q < NPF; ++q) {
+        gi[p][q] = 0;
+        if (ge0[p] + q < ge1[p]) gi[p][q] = g.indices[ge0[p] + q];
+      }
+  }
+  // araw: the raw chunks of a gathered slice's first edges (GATHER only)
+  auto load_regs = [&](int kk, uint4v ar[NAR], uint4v araw[NAR][NPF],
+                       uint4v br[4]) {
+    const int gk = kk + soff / 2;  // element index in K
 #pragma unroll
     for (int p = 0; p < NAR; ++p) {
       const int gr = r0 + srow + p * 32;
       ar[p] = {};
+      if constexpr (GATHER) {
+        if (kk < K1) {  // rows >= N have an empty edge range
+#pragma unroll
+          for (int q = 0; q < NPF; ++q) {
+            araw[p][q] = {};
+            if (ge0[p] + q < ge1[p])
+              araw[p][q] = *reinterpret_cast<const uint4v*>(
+                  A1 + (long)gi[p][q] * g.lda + gk);
+          }
+          continue;
+        }
+      }
       if (gr < N) {
-        const int gk = kk + soff / 2;  // element index in K
         const bf16* src = (gk < K1) ? (A1 + (long)gr * K1 + gk)
                                     : (A2 + (long)gr * (K - K1) + (gk - K1));
         ar[p] = *reinterpret_cast<const uint4v*>(src);
@@ -170,21 +275,35 @@ __device__ __forceinline__ void tile_regstaged_gemm(
     }
     tile_w_load<4, CT>(W, K, c0, kk, COL, tid, br);
   };
-  auto write_regs = [&](int i, const uint4v ar[NAR], const uint4v br[4]) {
+  auto write_regs = [&](int i, int kk, uint4v ar[NAR],
+                        const uint4v araw[NAR][NPF], const uint4v br[4]) {
+    if constexpr (GATHER) {
+      if (kk < K1) {
+        const int gk = kk + soff / 2;
+#pragma unroll
+        for (int p = 0; p < NAR; ++p) {
+          const int gr = r0 + srow + p * 32;
+          ar[p] = tile_gather_finish<NPF>(araw[p], A1 + gk, g.lda, g.indices, ge0[p],
+                                     ge1[p]);
+          if (g.out && gr < N)
+            *reinterpret_cast<uint4v*>(g.out + (long)gr * K1 + gk) = ar[p];
+        }
+      }
+    }
     tile_regs_store<NAR>(tile_abuf<BMT>(smem, i), tid, ar);
     tile_regs_store<4>(tile_bbuf<BMT>(smem, i), tid, br);
   };
-  uint4v areg[NAR], breg[4];
-  load_regs(0, areg, breg);
-  write_regs(0, areg, breg);
+  uint4v areg[NAR], areg2[NAR][NPF], breg[4];
+  load_regs(0, areg, areg2, breg);
+  write_regs(0, 0, areg, areg2, breg);
   __syncthreads();
   int cur = 0;
   for (int kk = 0; kk < K; kk += TILE_BK) {
     const bool has_next = (kk + TILE_BK) < K;
-    if (has_next) load_regs(kk + TILE_BK, areg, breg);
+    if (has_next) load_regs(kk + TILE_BK, areg, areg2, breg);
     tile_kstep<false>(acc, tile_abuf<BMT>(smem, cur), wm * (BMT / 2),
                       tile_bbuf<BMT>(smem, cur), wn * 64, lane);
-    if (has_next) write_regs(cur ^ 1, areg, breg);
+    if (has_next) write_regs(cur ^ 1, kk + TILE_BK, areg, areg2, breg);
     __syncthreads();
     cur ^= 1;
   }

@@ -33,8 +33,9 @@ ext = CUDAExtension(
         "csrc/graph_head.hip",
     ],
     # the shared tile core is included by gemm_bias, gemm_bf16, lmhead_ce and
-    # node_head: editing it rebuilds the extension
-    depends=["csrc/mfma_tile.h"],
+    # node_head, the gate backward by flowgnn_kernels and gemm_bias: editing
+    # either rebuilds the extension
+    depends=["csrc/mfma_tile.h", "csrc/gru_gate_bwd.h"],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
         "nvcc": ["-O3", "-std=c++17"],
