@@ -86,6 +86,11 @@ void launch_flash_dq(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_b
                      const __hip_bfloat16*, const int*, const float*, const float*, const float*,
                      __hip_bfloat16*, float*, int, int, int, float, int, unsigned,
                      unsigned long long, long, long, long, hipStream_t);
+// all six GGNN parameter grads at H = 128 in one launch (csrc/ggnn_wgrad.hip)
+void launch_ggnn_wgrad(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                       const __hip_bfloat16*, float*, float*, float*, float*, float*, float*,
+                       int, int, int, int, hipStream_t);
+int ggnn_wgrad_kchunk(int, int);
 void launch_wgrad2(const __hip_bfloat16*, const __hip_bfloat16*, float*, float*,
                    int, int, int, int, hipStream_t);
 void launch_adamw_fused(float*, const float*, float*, float*, long, float, float, float, float,
@@ -453,6 +458,84 @@ std::vector<at::Tensor> ggnn_fused_fwd(at::Tensor indptr, at::Tensor indices, at
   return {h_final, HH, M, R, Z, Nn, HN};
 }
 
+// The six GGNN parameter grads of K = S*N saved rows at H = 128, one launch.
+// gru_outs = [gW_ih, gW_hh, gb_ih, gb_hh] and out_we/out_be are live flat
+// .grad views the kernel adds into; without them fresh zero-filled tensors
+// are returned. Returns {gW_ih, gW_hh, gb_ih, gb_hh, gW_e, gb_e}.
+static std::vector<at::Tensor> ggnn_wgrad_run(const at::Tensor& Ggicat, const at::Tensor& M,
+                                              const at::Tensor& HH, const at::Tensor& Gwh,
+                                              long K, long H,
+                                              const c10::optional<at::Tensor>& out_we,
+                                              const c10::optional<at::Tensor>& out_be,
+                                              const c10::optional<std::vector<at::Tensor>>& gru_outs,
+                                              long kchunk = 0, long lds_epi = -1,
+                                              bool two_launches = false) {
+  TORCH_CHECK(H == 128, "ggnn_wgrad is written for H = 128");
+  TORCH_CHECK(out_be.has_value() == out_we.has_value(),
+              "ggnn_wgrad: out_we and out_be go together");
+  auto opts = Ggicat.options();
+  const bool gru_direct = gru_outs.has_value();
+  if (gru_direct)
+    TORCH_CHECK(gru_outs->size() == 4, "gru_outs = [gW_ih, gW_hh, gb_ih, gb_hh]");
+  auto pick = [&](int i) {
+    return gru_direct ? c10::optional<at::Tensor>((*gru_outs)[i]) : c10::nullopt;
+  };
+  auto gW_ih = acc_or_zeros(pick(0), {3 * H, H}, opts, "ggnn_wgrad gW_ih");
+  auto gW_hh = acc_or_zeros(pick(1), {3 * H, H}, opts, "ggnn_wgrad gW_hh");
+  auto gb_ih = acc_or_zeros(pick(2), {3 * H}, opts, "ggnn_wgrad gb_ih");
+  auto gb_hh = acc_or_zeros(pick(3), {3 * H}, opts, "ggnn_wgrad gb_hh");
+  auto gW_e = acc_or_zeros(out_we, {H, H}, opts, "ggnn_wgrad out_we");
+  auto gb_e = acc_or_zeros(out_be, {H}, opts, "ggnn_wgrad out_be");
+  if (two_launches) {  // the old pair on the same six buffers (probe A/B only)
+    launch_wgrad(ptr<bf16_t>(Ggicat), ptr<bf16_t>(M), ptr<bf16_t>(HH), nullptr, nullptr, K,
+                 4 * H, 2 * H, H, cur_stream(), gW_ih.data_ptr<float>(),
+                 gW_hh.data_ptr<float>(), gb_ih.data_ptr<float>(), gb_hh.data_ptr<float>());
+    launch_wgrad2(ptr<bf16_t>(Gwh), ptr<bf16_t>(HH), gW_e.data_ptr<float>(),
+                  gb_e.data_ptr<float>(), K, H, H, 1, cur_stream());
+    return {gW_ih, gW_hh, gb_ih, gb_hh, gW_e, gb_e};
+  }
+  // live views: the r/z column sums are added to both biases by the kernel.
+  // Fresh tensors: added to gb_ih only and copied, so that the two returned
+  // halves are the same bits (atomic order would otherwise differ).
+  launch_ggnn_wgrad(ptr<bf16_t>(Ggicat), ptr<bf16_t>(Gwh), ptr<bf16_t>(M), ptr<bf16_t>(HH),
+                    gW_ih.data_ptr<float>(), gW_hh.data_ptr<float>(), gW_e.data_ptr<float>(),
+                    gb_ih.data_ptr<float>(), gb_hh.data_ptr<float>(), gb_e.data_ptr<float>(),
+                    (int)K, gru_direct ? 1 : 0, (int)kchunk, (int)lds_epi, cur_stream());
+  if (!gru_direct) gb_hh.narrow(0, 0, 2 * H).copy_(gb_ih.narrow(0, 0, 2 * H));
+  return {gW_ih, gW_hh, gb_ih, gb_hh, gW_e, gb_e};
+}
+
+// raw binding of the kernel alone, for tests and tools/ggnn_wgrad_probe.py.
+// HH may carry more slabs than S (the loop's HH has S + 1); only the first
+// S*N rows of any operand are read. kchunk = 0 / lds_epi = -1 (K rows per
+// chunk, LDS-staged epilogue): the launcher's defaults.
+// two_launches runs the wgrad_kernel + wgrad2_kernel pair it replaced on the
+// same buffers, for a same-build timing A/B.
+std::vector<at::Tensor> ggnn_wgrad(at::Tensor Ggicat, at::Tensor M, at::Tensor HH,
+                                   at::Tensor Gwh, long S,
+                                   c10::optional<at::Tensor> out_we,
+                                   c10::optional<at::Tensor> out_be,
+                                   c10::optional<std::vector<at::Tensor>> gru_outs,
+                                   long kchunk, long lds_epi, bool two_launches) {
+  CHECK_GPU(Ggicat);
+  CHECK_GPU(M);
+  CHECK_GPU(HH);
+  CHECK_GPU(Gwh);
+  for (const at::Tensor* t : {&Ggicat, &M, &HH, &Gwh})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->dim() == 3, "ggnn_wgrad: (S, N, cols) bf16");
+  const long N = M.size(1);
+  const long H = M.size(2);
+  TORCH_CHECK(S >= 0 && Ggicat.size(0) >= S && M.size(0) >= S && HH.size(0) >= S &&
+                  Gwh.size(0) >= S,
+              "ggnn_wgrad: fewer than S slabs");
+  TORCH_CHECK(Ggicat.size(1) == N && HH.size(1) == N && Gwh.size(1) == N &&
+                  Ggicat.size(2) == 4 * H && HH.size(2) == H && Gwh.size(2) == H,
+              "ggnn_wgrad: operand shapes disagree");
+  TORCH_CHECK(S * N < (1L << 31), "ggnn_wgrad: S*N must fit an int");
+  return ggnn_wgrad_run(Ggicat, M, HH, Gwh, S * N, H, out_we, out_be, gru_outs, kchunk,
+                        lds_epi, two_launches);
+}
+
 std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
                                        at::Tensor t_indices, at::Tensor x, at::Tensor W_eT,
                                        at::Tensor WcatT, at::Tensor HH,
@@ -461,7 +544,7 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
                                        c10::optional<at::Tensor> out_we,
                                        c10::optional<at::Tensor> out_be,
                                        c10::optional<std::vector<at::Tensor>> gru_outs,
-                                       bool fuse) {
+                                       bool fuse, bool fused_wgrad) {
   const long N = x.size(0);
   const long H = x.size(1);
   const long S = n_steps;
@@ -521,7 +604,17 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
                         mptr<bf16_t>(grad_h), N, H, H, H, stream);
     }
   }
-  // batched weight/bias grads over all steps (K = S*N)
+  // batched weight/bias grads over all steps (K = S*N). At H = 128 one
+  // launch forms the seven live 128 x 128 tiles and the five bias sums;
+  // fused_wgrad = false (and every other H) keeps the two launches below.
+  if (fused_wgrad && H == 128) {
+    auto g = ggnn_wgrad_run(Ggicat, M, HH, Gwh, S * N, H, out_we, out_be, gru_outs);
+    if (gru_outs.has_value()) {  // grads already accumulated in the flat views
+      auto none = at::empty({0}, opts.dtype(at::kFloat));
+      return {grad_h, g[4], g[5], none, none, none, none};
+    }
+    return {grad_h, g[4], g[5], g[0], g[1], g[2], g[3]};
+  }
   auto A_g = Ggicat.view({S * N, 4 * H});
   const bool gru_direct = gru_outs.has_value();
   at::Tensor gWcat, cs4;
@@ -536,11 +629,13 @@ std::vector<at::Tensor> ggnn_fused_bwd(at::Tensor grad_out, at::Tensor t_indptr,
     gWcat = at::zeros({4 * H, 2 * H}, opts.dtype(at::kFloat));
     cs4 = at::zeros({4 * H}, opts.dtype(at::kFloat));
   }
-  // bias grads (column sums of the gate/message grads) ride along in the
-  // wgrad kernels' A-tile staging — no separate colsum pass. The gate
-  // wgrad is a SPLIT-B product (no [m|h] concat) so it stays on the
-  // generic split-K kernel; the W_e grad (plain A^T B, 128x128) takes the
-  // tr16-subtiled wgrad2 (K tails zero-filled in staging).
+  // The two-launch path: H = 64, 192, ... and the fused_wgrad = false A/B.
+  // Bias grads (column sums of the gate/message grads) ride along in the
+  // wgrad kernels' A-tile staging. The gate wgrad is the packed (4H, 2H)
+  // SPLIT-B product with the GRU scatter epilogue, which only the generic
+  // bounds-checked split-K kernel has (it also computes the two dead
+  // tiles); the W_e grad (plain A^T B) takes the tr16-subtiled wgrad2 where
+  // H is a multiple of 128 (K tails zero-filled in staging).
   if (gru_direct)
     launch_wgrad(ptr<bf16_t>(A_g), ptr<bf16_t>(M), ptr<bf16_t>(HH), nullptr, nullptr,
                  S * N, 4 * H, 2 * H, H, stream, (*gru_outs)[0].data_ptr<float>(),
@@ -1654,5 +1749,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("HN"), pybind11::arg("n_steps"),
         pybind11::arg("out_we") = pybind11::none(),
         pybind11::arg("out_be") = pybind11::none(),
-        pybind11::arg("gru_outs") = pybind11::none(), pybind11::arg("fuse") = true);
+        pybind11::arg("gru_outs") = pybind11::none(), pybind11::arg("fuse") = true,
+        pybind11::arg("fused_wgrad") = true);
+  m.def("ggnn_wgrad", &ggnn_wgrad, pybind11::arg("Ggicat"), pybind11::arg("M"),
+        pybind11::arg("HH"), pybind11::arg("Gwh"), pybind11::arg("S"),
+        pybind11::arg("out_we") = pybind11::none(), pybind11::arg("out_be") = pybind11::none(),
+        pybind11::arg("gru_outs") = pybind11::none(), pybind11::arg("kchunk") = 0,
+        pybind11::arg("lds_epi") = -1, pybind11::arg("two_launches") = false);
+  // K rows per chunk the launcher uses for a K-row problem (kchunk = 0: its rule)
+  m.def("ggnn_wgrad_kchunk", [](int64_t K, int64_t kchunk) {
+    return ggnn_wgrad_kchunk((int)K, (int)kchunk);
+  }, pybind11::arg("K"), pybind11::arg("kchunk") = 0);
 }

@@ -27,15 +27,16 @@ ext = CUDAExtension(
         "csrc/flash_attn.hip",
         "csrc/gemm_bf16.hip",
         "csrc/wgrad2.hip",
+        "csrc/ggnn_wgrad.hip",
         "csrc/adamw.hip",
         "csrc/lmhead_ce.hip",
         "csrc/node_head.hip",
         "csrc/graph_head.hip",
     ],
     # the shared tile core is included by gemm_bias, gemm_bf16, lmhead_ce and
-    # node_head, the gate backward by flowgnn_kernels and gemm_bias: editing
-    # either rebuilds the extension
-    depends=["csrc/mfma_tile.h", "csrc/gru_gate_bwd.h"],
+    # node_head, the gate backward by flowgnn_kernels and gemm_bias, the tr16
+    # staging by wgrad2 and ggnn_wgrad: editing any rebuilds the extension
+    depends=["csrc/mfma_tile.h", "csrc/gru_gate_bwd.h", "csrc/wgrad_tr16.h"],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
         "nvcc": ["-O3", "-std=c++17"],
