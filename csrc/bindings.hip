@@ -107,6 +107,14 @@ void launch_softmax_mask_bwd(const T*, const T*, T*, long, int, float, float,
 void launch_flash_received(const __hip_bfloat16*, const __hip_bfloat16*, const int*, const float*,
                            const float*, float*, int, int, int, float, int, long, long,
                            hipStream_t);
+void launch_decode_self(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                        __hip_bfloat16*, __hip_bfloat16*, const int*, const float*,
+                        __hip_bfloat16*, long, int, int, int, float, long, long, long,
+                        hipStream_t);
+size_t decode_cross_lds_bytes(int);
+void launch_decode_cross(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                         const int*, __hip_bfloat16*, int, int, int, int, float, long, long, long,
+                         long, long, hipStream_t);
 void dkv_prof_fetch(unsigned long long*);
 void fwd_prof_fetch(unsigned long long*);
 template <typename T>
@@ -1033,6 +1041,113 @@ at::Tensor flash_attn_received(at::Tensor Q, at::Tensor K, at::Tensor lse, int64
   return R;
 }
 
+// ---------------------------------------------------------------------------
+// Decode attention (csrc/decode_attn.hip): one query row per sequence
+// ---------------------------------------------------------------------------
+
+// (R, H*64) bf16 row-strided view (a slice of a fused projection): last dim
+// contiguous, rows 16-B aligned. Returns the row stride.
+static long da_rows(const char* name, const at::Tensor& t, long R, int64_t H,
+                    const at::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kBFloat16,
+              name, " must be a bf16 tensor on q's device");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == R && t.size(1) == H * 64, name,
+              " must be (R, H*64) with head_dim 64");
+  TORCH_CHECK(t.stride(1) == 1 && (R == 1 || t.stride(0) >= t.size(1)) && t.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " must be a row-strided view with 16-B aligned rows");
+  return t.stride(0);
+}
+
+// Stores k_new / v_new into cache[r, pos] and returns the attention output of
+// the new token over keys 0..pos, (R, H*64) bf16, every element written.
+at::Tensor decode_self_attn(at::Tensor q, at::Tensor k_new, at::Tensor v_new, at::Tensor k_cache,
+                            at::Tensor v_cache, c10::optional<at::Tensor> anc,
+                            c10::optional<at::Tensor> bias_dist, int64_t pos, int64_t H,
+                            double scale) {
+  TORCH_CHECK(H >= 1 && H <= 65535, "decode_self_attn: bad head count");
+  TORCH_CHECK(q.dim() == 2, "decode_self_attn: q must be (R, H*64)");
+  const long R = q.size(0);
+  const long ldq = da_rows("decode_self_attn: q", q, R, H, q);
+  const long ldk = da_rows("decode_self_attn: k_new", k_new, R, H, q);
+  const long ldv = da_rows("decode_self_attn: v_new", v_new, R, H, q);
+  for (const at::Tensor* c : {&k_cache, &v_cache})
+    TORCH_CHECK(c->is_cuda() && c->device() == q.device() && c->scalar_type() == at::kBFloat16 &&
+                    c->is_contiguous() && c->dim() == 3 && c->size(0) == R &&
+                    c->size(2) == H * 64 && c->size(1) == k_cache.size(1),
+                "decode_self_attn: caches must be contiguous bf16 (R, Tmax, H*64) on q's device");
+  const long Tmax = k_cache.size(1);
+  TORCH_CHECK(pos >= 0 && pos < Tmax, "decode_self_attn: pos must be in [0, Tmax)");
+  TORCH_CHECK(Tmax <= 8192, "decode_self_attn: Tmax above 8192");
+  const int* aptr = nullptr;
+  if (anc.has_value()) {
+    TORCH_CHECK(anc->is_cuda() && anc->device() == q.device() && anc->scalar_type() == at::kInt &&
+                    anc->is_contiguous() && anc->dim() == 2 && anc->size(0) == R &&
+                    anc->size(1) == Tmax,
+                "decode_self_attn: anc must be a contiguous int32 (R, Tmax) tensor on q's device");
+    aptr = anc->data_ptr<int>();
+  }
+  const float* bptr = nullptr;
+  if (bias_dist.has_value()) {
+    TORCH_CHECK(bias_dist->is_cuda() && bias_dist->device() == q.device() &&
+                    bias_dist->scalar_type() == at::kFloat && bias_dist->is_contiguous() &&
+                    bias_dist->dim() == 2 && bias_dist->size(0) == H &&
+                    bias_dist->size(1) == Tmax,
+                "decode_self_attn: bias_dist must be a contiguous fp32 (H, Tmax) tensor");
+    bptr = bias_dist->data_ptr<float>();
+  }
+  auto out = at::empty({R, H * 64}, q.options());
+  if (R == 0) return out;
+  launch_decode_self(ptr<bf16_t>(q), ptr<bf16_t>(k_new), ptr<bf16_t>(v_new),
+                     mptr<bf16_t>(k_cache), mptr<bf16_t>(v_cache), aptr, bptr, mptr<bf16_t>(out),
+                     R, (int)Tmax, (int)pos, (int)H, (float)scale, ldq, ldk, ldv, cur_stream());
+  return out;
+}
+
+// (B, Lk, H*64) bf16 view of a fused K/V buffer: last dim contiguous, 16-B
+// aligned rows, any batch stride
+static void da_kv(const char* name, const at::Tensor& t, int64_t H, const at::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kBFloat16,
+              name, " must be a bf16 tensor on q's device");
+  TORCH_CHECK(t.dim() == 3 && t.size(2) == H * 64, name, " must be (B, Lk, H*64)");
+  TORCH_CHECK(t.stride(2) == 1 && t.stride(1) >= t.size(2) && t.stride(1) % 8 == 0 &&
+                  t.stride(0) % 8 == 0 && t.stride(0) >= 0 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " must be a row-strided view with 16-B aligned rows");
+}
+
+// Row r = b * beams + i attends over source b's keys < valid[b]; (R, H*64)
+// bf16, every element written (exact zeros where valid[b] == 0).
+at::Tensor decode_cross_attn(at::Tensor q, at::Tensor k, at::Tensor v,
+                             c10::optional<at::Tensor> valid, int64_t beams, int64_t H,
+                             double scale) {
+  TORCH_CHECK(H >= 1 && H <= 65535, "decode_cross_attn: bad head count");
+  TORCH_CHECK(q.dim() == 2, "decode_cross_attn: q must be (R, H*64)");
+  const long R = q.size(0);
+  const long ldq = da_rows("decode_cross_attn: q", q, R, H, q);
+  da_kv("decode_cross_attn: k", k, H, q);
+  da_kv("decode_cross_attn: v", v, H, q);
+  const long B = k.size(0), Lk = k.size(1);
+  TORCH_CHECK(v.size(0) == B && v.size(1) == Lk, "decode_cross_attn: k and v shapes differ");
+  TORCH_CHECK(beams >= 1 && R == B * beams, "decode_cross_attn: R must be B * beams");
+  TORCH_CHECK(Lk >= 1 && decode_cross_lds_bytes((int)std::min<long>(Lk, 1 << 20)) <= 65536,
+              "decode_cross_attn: Lk must be in [1, 768]");
+  const int* vptr = nullptr;
+  if (valid.has_value()) {
+    TORCH_CHECK(valid->is_cuda() && valid->device() == q.device() &&
+                    valid->scalar_type() == at::kInt && valid->is_contiguous() &&
+                    valid->numel() == B,
+                "decode_cross_attn: valid must hold B int32 lengths on q's device");
+    vptr = valid->data_ptr<int>();
+  }
+  auto out = at::empty({R, H * 64}, q.options());
+  if (R == 0) return out;
+  launch_decode_cross(ptr<bf16_t>(q), ptr<bf16_t>(k), ptr<bf16_t>(v), vptr, mptr<bf16_t>(out),
+                      (int)B, (int)Lk, (int)beams, (int)H, (float)scale, ldq, k.stride(1),
+                      v.stride(1), k.stride(0), v.stride(0), cur_stream());
+  return out;
+}
+
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor dO, at::Tensor Q, at::Tensor K, at::Tensor V,
                                        at::Tensor O, at::Tensor lse, int64_t H,
                                        c10::optional<at::Tensor> valid,
@@ -1550,6 +1665,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("rstd"), pybind11::arg("out") = pybind11::none());
   m.def("flash_attn_fwd", &flash_attn_fwd);
   m.def("flash_attn_received", &flash_attn_received);
+  m.def("decode_self_attn", &decode_self_attn);
+  m.def("decode_cross_attn", &decode_cross_attn);
   m.def("flash_attn_bwd", &flash_attn_bwd, pybind11::arg("dO"), pybind11::arg("Q"),
         pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("O"), pybind11::arg("lse"),
         pybind11::arg("H"), pybind11::arg("valid"), pybind11::arg("bias"),

@@ -183,6 +183,59 @@ class T5Attention(nn.Module):
         ctx = torch.matmul(probs, v).transpose(1, 2).reshape(B, Lq, H * d)
         return fused_linear(ctx, self.o.weight)
 
+    def decode_bias_table(self, t_max, device):
+        """(H, t_max) fp32 table for the in-place decode path: entry [h, dist]
+        is the bias of a key `dist` positions behind the query (causal
+        buckets), i.e. compute_bias(t, t)[0, h, t - 1, t - 1 - dist]. Built
+        once per generate call instead of one bucket computation per token."""
+        dist = torch.arange(t_max, dtype=torch.long, device=device)
+        buckets = t5_relative_position_bucket(
+            -dist, bidirectional=False,
+            num_buckets=self.cfg.relative_attention_num_buckets,
+            max_distance=self.cfg.relative_attention_max_distance,
+        )
+        with torch.no_grad():
+            return self.relative_attention_bias.weight[buckets].t().float().contiguous()
+
+    def decode_self_indirect(self, x, k_cache, v_cache, anc, bias_dist, pos):
+        """Self-attention of the new token rows x (R, D) against the in-place
+        cache (ops.decode_self_attention): one fused q/k/v projection where
+        the GEMM geometry fits, three otherwise — the kernel takes either
+        through its row strides."""
+        from ..ops.transformer import decode_self_attention, fused_qkv
+
+        H, inner = self.cfg.num_heads, self.cfg.num_heads * self.cfg.d_kv
+        qkv = fused_qkv(x, self.q.weight, self.k.weight, self.v.weight)
+        if qkv is not None:
+            q, k, v = qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:]
+        else:
+            q = fused_linear(x, self.q.weight)
+            k = fused_linear(x, self.k.weight)
+            v = fused_linear(x, self.v.weight)
+        ctx = decode_self_attention(q, k, v, k_cache, v_cache, anc, bias_dist, pos, H, 1.0)
+        return fused_linear(ctx, self.o.weight)
+
+    def cross_kv(self, enc):
+        """(B, Lk, 2 * inner) cross-attention K | V of the encoder states,
+        once per source (not per beam)."""
+        from ..ops.transformer import fused_kv
+
+        kv = fused_kv(enc, self.k.weight, self.v.weight)
+        if kv is None:
+            kv = torch.cat([fused_linear(enc, self.k.weight),
+                            fused_linear(enc, self.v.weight)], dim=-1)
+        return kv
+
+    def decode_cross_indirect(self, x, kv, valid, beams):
+        """Cross-attention of the new token rows x (B * beams, D) over the
+        per-source `kv` of cross_kv (ops.decode_cross_attention)."""
+        from ..ops.transformer import decode_cross_attention
+
+        H, inner = self.cfg.num_heads, self.cfg.num_heads * self.cfg.d_kv
+        q = fused_linear(x, self.q.weight)
+        ctx = decode_cross_attention(q, kv[..., :inner], kv[..., inner:], valid, beams, H, 1.0)
+        return fused_linear(ctx, self.o.weight)
+
     def forward(self, x, valid, kv=None, position_bias=None, dropout_p=0.0,
                 bias_accum=None):
         B, Lq, _ = x.shape
@@ -367,6 +420,8 @@ class T5Stack(nn.Module):
                              self.embed_tokens.padding_idx)
         if x.is_cuda:
             x = x.to(torch.bfloat16)
+        if isinstance(state, _IndirectDecodeState):
+            return self._decode_step_indirect(x, state)
         t_new = state.t + 1
         attn0 = self.block[0].layer[0].SelfAttention
         # last-query-row bias only: compute_bias builds the (buckets, t*t)
@@ -391,6 +446,27 @@ class T5Stack(nn.Module):
             x = blk.layer[2](x)
         state.t = t_new
         return self.final_layer_norm(x)
+
+    def _decode_step_indirect(self, x, state: "_IndirectDecodeState"):
+        """decode_step on the in-place state: per block one fused self-attention
+        kernel (cache store + indirection + bias + softmax + PV) and one fused
+        cross-attention kernel over the per-source K/V."""
+        pos = state.t
+        if pos >= state.t_max:
+            raise ValueError("decode step past the state's max_length")
+        R = x.shape[0]
+        x = x.reshape(R, -1)
+        state.begin_step()
+        for i, blk in enumerate(self.block):
+            h = blk.layer[0].layer_norm(x)
+            x = x + blk.layer[0].SelfAttention.decode_self_indirect(
+                h, state.k[i], state.v[i], state.anc, state.bias_dist, pos)
+            h = blk.layer[1].layer_norm(x)
+            x = x + blk.layer[1].EncDecAttention.decode_cross_indirect(
+                h, state.cross[i], state.valid, state.beams)
+            x = blk.layer[2](x)
+        state.t = pos + 1
+        return self.final_layer_norm(x).unsqueeze(1)
 
 
 def _flash_bias_T(position_bias, bias_accum):
@@ -447,6 +523,54 @@ class _DecodeState:
                 for key in ("k", "v"):
                     if c[part].get(key) is not None:
                         c[part][key] = c[part][key].index_select(0, idx)
+
+
+class _IndirectDecodeState:
+    """In-place decode state (generate(kv_cache="indirect")).
+
+    k[i], v[i]  (R, max_length, inner) self-attention caches of block i,
+                allocated once; row r writes slot (r, t) at step t and no
+                slot is ever moved or rewritten.
+    anc         (R, max_length) int32, shared by all blocks (ancestry is the
+                same in every layer): anc[r, j] is the cache row holding
+                position j of row r's history. None for greedy (identity).
+    bias_dist   (H, max_length) relative-position bias by distance.
+    cross[i]    (B, Lk, 2 * inner) cross K | V of block i, once per SOURCE.
+
+    Beam reordering is one row gather on anc; no K/V moves."""
+
+    def __init__(self, decoder: "T5Stack", enc, enc_valid, beams: int, max_length: int):
+        cfg = decoder.cfg
+        B = enc.shape[0]
+        R = B * beams
+        inner = cfg.num_heads * cfg.d_kv
+        dev = enc.device
+        if enc.is_cuda:
+            enc = enc.to(torch.bfloat16)
+        self.beams, self.t, self.t_max = beams, 0, max_length
+        self.valid = enc_valid
+        n = len(decoder.block)
+        self.k = [torch.zeros(R, max_length, inner, dtype=enc.dtype, device=dev) for _ in range(n)]
+        self.v = [torch.zeros(R, max_length, inner, dtype=enc.dtype, device=dev) for _ in range(n)]
+        self.cross = [blk.layer[1].EncDecAttention.cross_kv(enc) for blk in decoder.block]
+        self.bias_dist = decoder.block[0].layer[0].SelfAttention.decode_bias_table(max_length, dev)
+        self.anc = None
+        if beams > 1:
+            self._rows = torch.arange(R, dtype=torch.int32, device=dev)
+            self.anc = self._rows.unsqueeze(1).repeat(1, max_length)
+            self._spare = torch.empty_like(self.anc)
+
+    def begin_step(self):
+        """Row r itself owns the slot it is about to write. (The kernel takes
+        the new token from registers, so this column is first read at the
+        next step, after reorder has gathered it.)"""
+        if self.anc is not None:
+            self.anc[:, self.t] = self._rows
+
+    def reorder(self, idx: torch.Tensor):
+        """Beam search: new row r continues old row idx[r]."""
+        torch.index_select(self.anc, 0, idx, out=self._spare)
+        self.anc, self._spare = self._spare, self.anc
 
 
 class T5ForConditionalGeneration(nn.Module):
@@ -509,28 +633,60 @@ class T5ForConditionalGeneration(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_length: int = 64,
-                 num_beams: int = 1):
+                 num_beams: int = 1, kv_cache: str = "auto"):
         """Greedy / beam-search generation (reference CodeT5 Beam,
         models.py:298-408 capability) with per-layer KV caches
         (T5Stack.decode_step): each step runs ONE decoder column instead of
         re-running the whole prefix — linear, not quadratic, in the
-        generated length. Beam search reorders the caches by beam index."""
+        generated length.
+
+        kv_cache selects how the caches are kept:
+          "concat"    grown by torch.cat each step, attention in eager torch;
+                      beam search index_selects every cached tensor.
+          "indirect"  allocated once and written in place; beam search gathers
+                      one small ancestry table and moves no K/V, the cross
+                      K/V are held once per source, and each attention is one
+                      fused kernel (csrc/decode_attn.hip) on the GPU.
+          "auto"      "indirect" where decode_attention_usable (GPU, head_dim
+                      64), else "concat".
+
+        On a GPU outside autocast this enters bf16 autocast itself: the decode
+        path computes in bf16 there against fp32 master weights."""
+        if kv_cache not in ("auto", "concat", "indirect"):
+            raise ValueError(f"kv_cache must be 'auto', 'concat' or 'indirect', not {kv_cache!r}")
+        if input_ids.is_cuda and not torch.is_autocast_enabled():
+            with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
+                return self._generate(input_ids, attention_mask, max_length, num_beams, kv_cache)
+        return self._generate(input_ids, attention_mask, max_length, num_beams, kv_cache)
+
+    def _generate(self, input_ids, attention_mask, max_length, num_beams, kv_cache):
+        from ..ops.transformer import decode_attention_usable
+
         if attention_mask is None:
             attention_mask = input_ids.ne(self.config.pad_token_id)
         enc_valid = attention_mask.sum(1).to(torch.int32)
         enc = self.encoder(input_ids, enc_valid)
+        if kv_cache == "auto":
+            kv_cache = "indirect" if decode_attention_usable(
+                enc, self.config.d_kv, enc.shape[1]) else "concat"
+        indirect = kv_cache == "indirect"
         B = input_ids.shape[0]
         device = input_ids.device
         eos, pad, start = (self.config.eos_token_id, self.config.pad_token_id,
                            self.config.decoder_start_token_id)
         scale = self.config.d_model ** -0.5 if self.config.tie_word_embeddings else 1.0
 
+        def new_state(beams):
+            if indirect:  # takes the UN-repeated encoder output
+                return _IndirectDecodeState(self.decoder, enc, enc_valid, beams, max_length)
+            return _DecodeState(len(self.decoder.block))
+
         def step_logits(cur, enc_rep, valid_rep, state):
             h = self.decoder.decode_step(cur, enc_rep, valid_rep, state)[:, -1]
             return self.lm_head(h.float() * scale if scale != 1.0 else h.float())
 
         if num_beams <= 1:
-            state = _DecodeState(len(self.decoder.block))
+            state = new_state(1)
             seq = torch.full((B, 1), start, dtype=torch.long, device=device)
             cur = seq
             done = torch.zeros(B, dtype=torch.bool, device=device)
@@ -545,9 +701,12 @@ class T5ForConditionalGeneration(nn.Module):
             return seq
         # beam search
         K = num_beams
-        enc_rep = enc.repeat_interleave(K, dim=0)
-        valid_rep = enc_valid.repeat_interleave(K)
-        state = _DecodeState(len(self.decoder.block))
+        if indirect:
+            enc_rep = valid_rep = None  # cross K/V stay per source
+        else:
+            enc_rep = enc.repeat_interleave(K, dim=0)
+            valid_rep = enc_valid.repeat_interleave(K)
+        state = new_state(K)
         seq = torch.full((B * K, 1), start, dtype=torch.long, device=device)
         cur = seq
         beam_scores = torch.full((B, K), -1e9, device=device)

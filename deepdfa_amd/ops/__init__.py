@@ -2,6 +2,9 @@ from ._ext import has_ext, load_ext
 from .flowgnn import attn_pool, embed4, gru_cell, segment_max, spmm_sum
 from .transformer import (
     attention_received,
+    decode_attention_usable,
+    decode_cross_attention,
+    decode_self_attention,
     flash_attention_received,
     flash_attention_received_qkv,
 )
@@ -17,4 +20,7 @@ __all__ = [
     "attention_received",
     "flash_attention_received",
     "flash_attention_received_qkv",
+    "decode_self_attention",
+    "decode_cross_attention",
+    "decode_attention_usable",
 ]

@@ -728,6 +728,105 @@ def flash_attention_received_qkv(qkv, num_heads, valid=None, bias=None, scale=1.
         return flash_attention_received(q, k, v, num_heads, valid, bias, scale, causal)
 
 
+DECODE_CROSS_MAX_LK = 768  # the cross kernel parks 16 x Lk fp32 scores in 64 KB of LDS
+
+
+def decode_attention_usable(x, d_kv, Lk=None) -> bool:
+    """True where the decode attention kernels (csrc/decode_attn.hip) serve
+    `x`: CUDA, bf16, head_dim 64 (and a source length the cross kernel holds)."""
+    return (
+        x.is_cuda
+        and x.dtype == torch.bfloat16
+        and d_kv == 64
+        and (Lk is None or 1 <= Lk <= DECODE_CROSS_MAX_LK)
+    )
+
+
+def _decode_compute_dtype(q):
+    return torch.float64 if q.dtype == torch.float64 else torch.float32
+
+
+def decode_self_attention(q, k_new, v_new, k_cache, v_cache, anc, bias_dist, pos,
+                          num_heads, scale=1.0):
+    """One decoding step of causal self-attention with an in-place KV cache.
+
+    q, k_new, v_new (R, H*d) are the new token's projections (row-strided
+    views are fine). The call stores k_new / v_new into cache[r, pos] of the
+    (R, Tmax, H*d) caches and returns the (R, H*d) attention output over keys
+    0..pos. Key j < pos of row r is read from cache[anc[r, j], j]: `anc`
+    (int32 (R, Tmax), or None for identity) is the beam-search indirection
+    table, so reordering beams never moves K/V. Key pos is the new token
+    itself. `bias_dist` (fp32 (H, Tmax), or None) adds bias_dist[h, pos - j]
+    to the score of key j. Inference only: ValueError with grad enabled on an
+    input that requires grad.
+
+    On the GPU this is decode_self_kernel (bf16, d = 64); elsewhere the same
+    contract in plain torch, computed in fp32 (fp64 for fp64 inputs)."""
+    _no_grad_inputs("decode_self_attention", q, k_new, v_new, k_cache, v_cache, bias_dist)
+    H = num_heads
+    with torch.no_grad():
+        if q.is_cuda:
+            ext = load_ext(required=True)
+            return ext.decode_self_attn(q, k_new, v_new, k_cache, v_cache, anc, bias_dist,
+                                        int(pos), H, float(scale))
+        R, D = q.shape
+        d = D // H
+        Tmax = k_cache.shape[1]
+        if not 0 <= pos < Tmax:
+            raise ValueError("pos must be in [0, Tmax)")
+        k_cache[:, pos] = k_new
+        v_cache[:, pos] = v_new
+        T = pos + 1
+        ct = _decode_compute_dtype(q)
+        if anc is None:
+            kh, vh = k_cache[:, :T], v_cache[:, :T]
+        else:
+            rows = anc[:, :T].long().clone()
+            rows[:, pos] = torch.arange(R, device=q.device)  # the new token: own row
+            cols = torch.arange(T, device=q.device).unsqueeze(0)
+            kh, vh = k_cache[rows, cols], v_cache[rows, cols]
+        s = torch.einsum("rhd,rthd->rht", q.to(ct).view(R, H, d),
+                         kh.to(ct).view(R, T, H, d)) * scale
+        if bias_dist is not None:
+            s = s + bias_dist[:, pos - torch.arange(T, device=q.device)].to(ct)
+        p = torch.softmax(s, dim=-1)
+        out = torch.einsum("rht,rthd->rhd", p, vh.to(ct).view(R, T, H, d))
+        return out.reshape(R, D).to(q.dtype)
+
+
+def decode_cross_attention(q, k, v, valid, beams, num_heads, scale=1.0):
+    """One decoding step of cross-attention over K/V stored once per SOURCE.
+
+    q (R, H*d) with R = B * beams; k, v (B, Lk, H*d), e.g. the two halves of a
+    fused_kv buffer. Row r attends over source r // beams (the
+    repeat_interleave order of generate). Keys >= valid[b] get probability
+    exactly 0; a source with valid[b] == 0 returns exact zeros (the eager
+    softmax over an all-masked row gives NaN instead). Inference only.
+
+    On the GPU this is decode_cross_kernel (bf16, d = 64, Lk <= 768);
+    elsewhere plain torch in fp32 (fp64 for fp64 inputs)."""
+    _no_grad_inputs("decode_cross_attention", q, k, v)
+    H = num_heads
+    with torch.no_grad():
+        if q.is_cuda:
+            ext = load_ext(required=True)
+            return ext.decode_cross_attn(q, k, v, valid, int(beams), H, float(scale))
+        R, D = q.shape
+        B, Lk, _ = k.shape
+        if beams < 1 or R != B * beams:
+            raise ValueError("q must hold B * beams rows")
+        d = D // H
+        ct = _decode_compute_dtype(q)
+        s = torch.einsum("bihd,bkhd->bhik", q.to(ct).view(B, beams, H, d),
+                         k.to(ct).view(B, Lk, H, d)) * scale
+        if valid is not None:
+            dead = torch.arange(Lk, device=q.device).view(1, 1, 1, Lk) >= valid.view(-1, 1, 1, 1)
+            s = s.masked_fill(dead, float("-inf"))
+        p = torch.nan_to_num(torch.softmax(s, dim=-1), nan=0.0)
+        out = torch.einsum("bhik,bkhd->bihd", p, v.to(ct).view(B, Lk, H, d))
+        return out.reshape(R, D).to(q.dtype)
+
+
 class _LMHeadCE(torch.autograd.Function):
     """K21: fused LM-head GEMM + cross-entropy over the 32100-token vocab
     (csrc/lmhead_ce.hip). Forward streams vocab tiles with online
