@@ -107,6 +107,19 @@ void launch_softmax_mask_bwd(const T*, const T*, T*, long, int, float, float,
 void launch_flash_received(const __hip_bfloat16*, const __hip_bfloat16*, const int*, const float*,
                            const float*, float*, int, int, int, float, int, long, long,
                            hipStream_t);
+// general (Lq, Lk) flash attention (csrc/flash_rect.hip)
+void launch_flash_rect_fwd(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                           const int*, const float*, __hip_bfloat16*, float*, int, int, int, int,
+                           float, int, unsigned, unsigned long long, long, long, hipStream_t);
+void launch_flash_rect_dq(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                          const __hip_bfloat16*, const int*, const float*, const float*,
+                          const float*, __hip_bfloat16*, float*, int, int, int, int, float, int,
+                          unsigned, unsigned long long, long, long, hipStream_t);
+void launch_flash_rect_dkv(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
+                           const __hip_bfloat16*, const int*, const float*, const float*,
+                           const float*, __hip_bfloat16*, __hip_bfloat16*, int, int, int, int,
+                           float, int, unsigned, unsigned long long, long, long, long,
+                           hipStream_t);
 void launch_decode_self(const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
                         __hip_bfloat16*, __hip_bfloat16*, const int*, const float*,
                         __hip_bfloat16*, long, int, int, int, float, long, long, long,
@@ -1231,6 +1244,171 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor dO, at::Tensor Q, at::Tensor K
   return {dQ, dK, dV};
 }
 
+// ---------------------------------------------------------------------------
+// General flash attention (csrc/flash_rect.hip): any Lq >= 1, Lk >= 1
+// ---------------------------------------------------------------------------
+
+struct FlashRectArgs {
+  int B, Lq, Lk;
+  long ldq, ldkv;
+  const int* valid;
+  const float* bias;
+};
+
+// Shape, dtype and layout checks shared by flash_rect_fwd / flash_rect_bwd.
+// Argument-shape errors come before the device checks.
+static FlashRectArgs flash_rect_check(const char* fn, const at::Tensor& Q, const at::Tensor& K,
+                                      const at::Tensor& V, int64_t H,
+                                      const c10::optional<at::Tensor>& valid,
+                                      const c10::optional<at::Tensor>& bias, bool causal,
+                                      double dropout_p) {
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16 && K.scalar_type() == at::kBFloat16 &&
+                  V.scalar_type() == at::kBFloat16,
+              fn, ": Q, K and V must be bf16");
+  TORCH_CHECK(Q.dim() == 3 && K.dim() == 3 && V.dim() == 3, fn,
+              ": Q must be (B, Lq, H*64), K and V (B, Lk, H*64)");
+  TORCH_CHECK(H >= 1 && Q.size(2) == H * 64 && K.size(2) == H * 64, fn,
+              ": head_dim must be 64");
+  TORCH_CHECK(K.sizes() == V.sizes() && K.stride(1) == V.stride(1), fn,
+              ": K and V must have the same shape and row stride");
+  FlashRectArgs a;
+  TORCH_CHECK(K.size(0) == Q.size(0), fn, ": Q and K differ in batch size");
+  TORCH_CHECK(Q.size(1) >= 1 && K.size(1) >= 1 && Q.size(1) < (1 << 30) && K.size(1) < (1 << 30),
+              fn, ": Lq and Lk must be >= 1");
+  a.B = Q.size(0);
+  a.Lq = Q.size(1);
+  a.Lk = K.size(1);
+  TORCH_CHECK((long)a.B * H <= 65535, fn, ": B*H must not exceed 65535");
+  TORCH_CHECK(!causal || a.Lq == a.Lk, fn, ": causal needs Lq == Lk");
+  TORCH_CHECK(!bias.has_value() || a.Lq == a.Lk, fn, ": bias needs Lq == Lk");
+  TORCH_CHECK(dropout_p >= 0.0 && dropout_p < 1.0, fn, ": dropout_p must be in [0, 1)");
+  a.bias = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->is_contiguous(), fn,
+                ": bias must be contiguous fp32");
+    TORCH_CHECK(bias->numel() == H * (long)a.Lk * a.Lq, fn,
+                ": bias must be key-major (H, Lk, Lq)");
+  }
+  a.valid = nullptr;
+  if (valid.has_value())
+    TORCH_CHECK(valid->scalar_type() == at::kInt && valid->is_contiguous() &&
+                    valid->numel() == a.B,
+                fn, ": valid must be a contiguous int32 tensor of B lengths");
+  for (const at::Tensor* t : {&Q, &K, &V})
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) >= t->size(2) && t->stride(1) % 8 == 0 &&
+                    (t->size(0) == 1 || t->stride(0) == t->size(1) * t->stride(1)),
+                fn, ": flash tensor must be a (B, L, D) row-strided view");
+  TORCH_CHECK(Q.is_cuda() && K.device() == Q.device() && V.device() == Q.device(), fn,
+              ": Q, K and V must be on one GPU");
+  for (const at::Tensor* t : {&Q, &K, &V})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, fn,
+                ": flash tensor rows must be 16-B aligned");
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->device() == Q.device(), fn, ": bias must be on Q's device");
+    a.bias = bias->data_ptr<float>();
+  }
+  if (valid.has_value()) {
+    TORCH_CHECK(valid->device() == Q.device(), fn, ": valid must be on Q's device");
+    a.valid = valid->data_ptr<int>();
+  }
+  a.ldq = Q.stride(1);
+  a.ldkv = K.stride(1);
+  return a;
+}
+
+// [O (B, Lq, H*64) bf16, lse (B, H, Lq) fp32], every element written
+std::vector<at::Tensor> flash_rect_fwd(at::Tensor Q, at::Tensor K, at::Tensor V, int64_t H,
+                                       c10::optional<at::Tensor> valid,
+                                       c10::optional<at::Tensor> bias, double scale, bool causal,
+                                       double dropout_p, int64_t seed) {
+  const FlashRectArgs a =
+      flash_rect_check("flash_rect_fwd", Q, K, V, H, valid, bias, causal, dropout_p);
+  auto O = at::empty({a.B, a.Lq, H * 64}, Q.options());
+  auto lse = at::empty({a.B, H, a.Lq}, Q.options().dtype(at::kFloat));
+  if (a.B == 0) return {O, lse};
+  launch_flash_rect_fwd(ptr<bf16_t>(Q), ptr<bf16_t>(K), ptr<bf16_t>(V), a.valid, a.bias,
+                        mptr<bf16_t>(O), lse.data_ptr<float>(), a.B, (int)H, a.Lq, a.Lk,
+                        (float)scale, causal ? 1 : 0, (unsigned)(dropout_p * 256.0),
+                        (unsigned long long)seed, a.ldq, a.ldkv, cur_stream());
+  return {O, lse};
+}
+
+// [dQ, dK, dV, (dBias)], or with kv_fused [dQ, dKV (B, Lk, 2*H*64)]; every
+// element written, dK/dV rows of keys >= valid[b] exact zeros. dBias (fp32
+// atomics) goes into dbias_accum when given, else into a fresh (H, L, L).
+std::vector<at::Tensor> flash_rect_bwd(at::Tensor dO, at::Tensor Q, at::Tensor K, at::Tensor V,
+                                       at::Tensor O, at::Tensor lse, int64_t H,
+                                       c10::optional<at::Tensor> valid,
+                                       c10::optional<at::Tensor> bias, double scale, bool causal,
+                                       double dropout_p, int64_t seed, bool need_dbias,
+                                       c10::optional<at::Tensor> dbias_accum = c10::nullopt,
+                                       bool kv_fused = false) {
+  const FlashRectArgs a =
+      flash_rect_check("flash_rect_bwd", Q, K, V, H, valid, bias, causal, dropout_p);
+  const long HD64 = (long)H * 64;
+  for (const at::Tensor* t : {&dO, &O})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16 && t->is_contiguous() &&
+                    t->device() == Q.device() && t->dim() == 3 && t->size(0) == a.B &&
+                    t->size(1) == a.Lq && t->size(2) == HD64,
+                "flash_rect_bwd: dO and O must be contiguous bf16 (B, Lq, H*64) on Q's device");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.device() == Q.device() && lse.dim() == 3 && lse.size(0) == a.B &&
+                  lse.size(1) == H && lse.size(2) == a.Lq,
+              "flash_rect_bwd: lse must be a contiguous fp32 (B, H, Lq) tensor on Q's device");
+  TORCH_CHECK(!kv_fused || a.ldkv == 2 * HD64,
+              "flash_rect_bwd: kv_fused expects k/v slices of one (B, Lk, 2D) buffer");
+  float* dbias_ptr = nullptr;
+  at::Tensor dBias;
+  if (dbias_accum.has_value()) {
+    TORCH_CHECK(bias.has_value(), "flash_rect_bwd: dbias_accum without a bias");
+    TORCH_CHECK(dbias_accum->scalar_type() == at::kFloat && dbias_accum->is_contiguous() &&
+                    dbias_accum->device() == Q.device() &&
+                    dbias_accum->numel() == H * (long)a.Lk * a.Lq,
+                "flash_rect_bwd: dbias_accum must be a contiguous fp32 (H, Lk, Lq) tensor");
+    dbias_ptr = dbias_accum->data_ptr<float>();
+  } else if (need_dbias) {
+    TORCH_CHECK(bias.has_value(), "flash_rect_bwd: need_dbias without a bias");
+    dBias = at::zeros({H, (long)a.Lk, (long)a.Lq}, Q.options().dtype(at::kFloat));
+    dbias_ptr = dBias.data_ptr<float>();
+  }
+  auto stream = cur_stream();
+  at::Tensor dKV, dK, dV;
+  auto dQ = at::empty({a.B, a.Lq, HD64}, Q.options());
+  long ld_dkv = HD64;
+  if (kv_fused) {
+    dKV = at::empty({a.B, a.Lk, 2 * HD64}, Q.options());
+    ld_dkv = 2 * HD64;
+    dK = dKV.narrow(2, 0, HD64);
+    dV = dKV.narrow(2, HD64, HD64);
+  } else {
+    dK = at::empty({a.B, a.Lk, HD64}, Q.options());
+    dV = at::empty({a.B, a.Lk, HD64}, Q.options());
+  }
+  if (a.B > 0) {
+    auto Dterm = at::empty({a.B, H, a.Lq}, Q.options().dtype(at::kFloat));
+    launch_flash_dterm(ptr<bf16_t>(dO), ptr<bf16_t>(O), Dterm.data_ptr<float>(), a.B, (int)H,
+                       a.Lq, stream);
+    const unsigned p8 = (unsigned)(dropout_p * 256.0);
+    launch_flash_rect_dq(ptr<bf16_t>(Q), ptr<bf16_t>(K), ptr<bf16_t>(V), ptr<bf16_t>(dO), a.valid,
+                         a.bias, lse.data_ptr<float>(), Dterm.data_ptr<float>(),
+                         mptr<bf16_t>(dQ), dbias_ptr, a.B, (int)H, a.Lq, a.Lk, (float)scale,
+                         causal ? 1 : 0, p8, (unsigned long long)seed, a.ldq, a.ldkv, stream);
+    launch_flash_rect_dkv(ptr<bf16_t>(Q), ptr<bf16_t>(K), ptr<bf16_t>(V), ptr<bf16_t>(dO),
+                          a.valid, a.bias, lse.data_ptr<float>(), Dterm.data_ptr<float>(),
+                          mptr<bf16_t>(dK), mptr<bf16_t>(dV), a.B, (int)H, a.Lq, a.Lk,
+                          (float)scale, causal ? 1 : 0, p8, (unsigned long long)seed, a.ldq,
+                          a.ldkv, ld_dkv, stream);
+  }
+  const bool ret_dbias = need_dbias && !dbias_accum.has_value();
+  if (kv_fused) {
+    if (ret_dbias) return {dQ, dKV, dBias};
+    return {dQ, dKV};
+  }
+  if (ret_dbias) return {dQ, dK, dV, dBias};
+  return {dQ, dK, dV};
+}
+
+
 
 // out(N, COL) = A(N, K) @ W(COL, K)^T [+ bias] [+ addend] — transformer
 // shapes (csrc/gemm_bf16.hip). Geometry: N%128, K%64, COL%128 == 0.
@@ -1674,6 +1852,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("seed"), pybind11::arg("need_dbias"), pybind11::arg("fused_grads"),
         pybind11::arg("dbias_accum") = pybind11::none(),
         pybind11::arg("kv_fused") = false);
+  m.def("flash_rect_fwd", &flash_rect_fwd);
+  m.def("flash_rect_bwd", &flash_rect_bwd, pybind11::arg("dO"), pybind11::arg("Q"),
+        pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("O"), pybind11::arg("lse"),
+        pybind11::arg("H"), pybind11::arg("valid"), pybind11::arg("bias"),
+        pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("dropout_p"),
+        pybind11::arg("seed"), pybind11::arg("need_dbias"),
+        pybind11::arg("dbias_accum") = pybind11::none(), pybind11::arg("kv_fused") = false);
   m.def("lmhead_ce_fwd", &lmhead_ce_fwd);
   m.def("lmhead_ce_bwd", &lmhead_ce_bwd);
   m.def("relbias_wgrad", [](at::Tensor dbias, at::Tensor buckets, int64_t nb) {

@@ -32,6 +32,8 @@ from torch import nn
 from ..ops.transformer import (
     bias_gelu,
     flash_attention,
+    flash_attention_rect,
+    flash_rect_usable,
     flash_usable,
     fused_linear,
     layer_norm,
@@ -140,6 +142,11 @@ class RobertaSelfAttention(nn.Module):
         if d == 64 and not output_attentions and flash_usable(q, L):
             out = flash_attention(q, k, v, H, valid=valid, scale=1.0 / math.sqrt(d),
                                   dropout_p=p)
+            return out, None
+        if d == 64 and not output_attentions and flash_rect_usable(q, d):
+            # lengths off the 64 grid: the general kernels (csrc/flash_rect.hip)
+            out = flash_attention_rect(q, k, v, H, valid=valid, scale=1.0 / math.sqrt(d),
+                                       dropout_p=p)
             return out, None
         # materialized path: CPU / fp32 / attention-probs output
 

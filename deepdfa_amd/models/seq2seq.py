@@ -18,7 +18,8 @@ import math
 import torch
 import torch.nn as nn
 
-from ..ops.transformer import fused_linear, masked_softmax_dropout
+from ..ops.transformer import (flash_attention_rect, flash_rect_usable, fused_linear,
+                               masked_softmax_dropout)
 from .roberta import LayerNorm, RobertaConfig, RobertaModel, init_roberta_weights
 
 
@@ -40,11 +41,19 @@ class _MHA(nn.Module):
         kv = x if kv is None else kv
         B, Lq, D = x.shape
         Lk = kv.shape[1]
-        q = self.query(x).view(B, Lq, self.H, self.d).transpose(1, 2)
-        k = self.key(kv).view(B, Lk, self.H, self.d).transpose(1, 2)
-        v = self.value(kv).view(B, Lk, self.H, self.d).transpose(1, 2)
-        scores = torch.matmul(q, k.transpose(-1, -2))
         p = self.dropout_p if self.training else 0.0
+        q, k, v = self.query(x), self.key(kv), self.value(kv)
+        if self.d == 64 and flash_rect_usable(q, self.d) and k.dtype == q.dtype:
+            # fused attention at any (Lq, Lk): csrc/flash_rect.hip
+            if kv_valid is not None and kv_valid.dtype != torch.int32:
+                kv_valid = kv_valid.to(torch.int32)
+            return flash_attention_rect(q, k, v, self.H, valid=kv_valid,
+                                        scale=1.0 / math.sqrt(self.d), causal=causal,
+                                        dropout_p=p)
+        q = q.view(B, Lq, self.H, self.d).transpose(1, 2)
+        k = k.view(B, Lk, self.H, self.d).transpose(1, 2)
+        v = v.view(B, Lk, self.H, self.d).transpose(1, 2)
+        scores = torch.matmul(q, k.transpose(-1, -2))
         _, probs = masked_softmax_dropout(
             scores, kv_valid, 1.0 / math.sqrt(self.d), p, causal=causal
         )

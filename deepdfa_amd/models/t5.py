@@ -20,7 +20,9 @@ from dataclasses import dataclass
 import torch
 from torch import nn
 
-from ..ops.transformer import (dropout_add, flash_attention, flash_usable, fused_linear, masked_softmax_dropout, rms_norm)
+from ..ops.transformer import (dropout_add, flash_attention, flash_attention_rect,
+                               flash_attention_rect_kv, flash_rect_usable, flash_usable,
+                               fused_linear, masked_softmax_dropout, rms_norm)
 
 
 @dataclass
@@ -275,6 +277,16 @@ class T5Attention(nn.Module):
                 out = flash_attention_kv(qp, kvp, H, valid=valid, scale=1.0,
                                          dropout_p=dropout_p)
                 return fused_linear(out, self.o.weight)
+        elif (kv is not None and d == 64 and position_bias is None
+                and flash_rect_usable(qp, d)):
+            # the same at any other (Lq, Lk): the general kernels
+            from ..ops.transformer import fused_kv
+
+            kvp = fused_kv(src, self.k.weight, self.v.weight)
+            if kvp is not None:
+                out = flash_attention_rect_kv(qp, kvp, H, valid=valid, scale=1.0,
+                                              dropout_p=dropout_p)
+                return fused_linear(out, self.o.weight)
         kp = fused_linear(src, self.k.weight)
         vp = fused_linear(src, self.v.weight)
         if d == 64 and flash_usable(qp, Lq, Lk):
@@ -284,6 +296,16 @@ class T5Attention(nn.Module):
             out = flash_attention(qp, kp, vp, H, valid=valid, bias=bias, scale=1.0,
                                   causal=causal, dropout_p=dropout_p,
                                   bias_accum=bias_accum)
+            return fused_linear(out, self.o.weight)
+        if d == 64 and flash_rect_usable(qp, d):
+            # every other length (cross-attention with Lq != Lk, anything off
+            # the 64 grid): the general kernels, csrc/flash_rect.hip
+            bias = None
+            if position_bias is not None:
+                bias = _flash_bias_T(position_bias, bias_accum)
+            out = flash_attention_rect(qp, kp, vp, H, valid=valid, bias=bias, scale=1.0,
+                                       causal=causal, dropout_p=dropout_p,
+                                       bias_accum=bias_accum)
             return fused_linear(out, self.o.weight)
         q = split(qp, Lq)
         k = split(kp, Lk)

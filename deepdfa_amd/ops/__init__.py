@@ -7,6 +7,9 @@ from .transformer import (
     decode_self_attention,
     flash_attention_received,
     flash_attention_received_qkv,
+    flash_attention_rect,
+    flash_attention_rect_kv,
+    flash_rect_usable,
 )
 
 __all__ = [
@@ -20,6 +23,9 @@ __all__ = [
     "attention_received",
     "flash_attention_received",
     "flash_attention_received_qkv",
+    "flash_attention_rect",
+    "flash_attention_rect_kv",
+    "flash_rect_usable",
     "decode_self_attention",
     "decode_cross_attention",
     "decode_attention_usable",

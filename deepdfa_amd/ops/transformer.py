@@ -581,6 +581,137 @@ def flash_attention_kv(q, kv, num_heads, valid=None, scale=1.0, dropout_p=0.0):
     return _FlashAttentionKV.apply(q, kv, num_heads, valid, scale, dropout_p)
 
 
+def flash_rect_usable(x, d) -> bool:
+    """True where the general flash kernels (csrc/flash_rect.hip) serve `x`:
+    CUDA, bf16, head_dim 64; any query and key length."""
+    return x.is_cuda and x.dtype == torch.bfloat16 and d == 64
+
+
+def _attention_rect_torch(q, k, v, H, valid, bias, scale, causal, dropout_p):
+    """The flash_rect contract as a torch composition (CPU / oracle path):
+    q (B, Lq, H*d), k, v (B, Lk, H*d), bias key-major (H, Lk, Lq). Keys >=
+    min(valid[b], Lk) and, with causal, keys > q are masked; a row with no
+    unmasked key gives 0. Computed in fp32 (fp64 for fp64 inputs)."""
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    d = D // H
+    if (causal or bias is not None) and Lq != Lk:
+        raise ValueError("causal and bias need Lq == Lk")
+    if k.shape != v.shape or k.shape[0] != B or k.shape[2] != D:
+        raise ValueError("k and v must both be (B, Lk, H*d)")
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    qh = q.to(ct).view(B, Lq, H, d).transpose(1, 2)
+    kh = k.to(ct).view(B, Lk, H, d).transpose(1, 2)
+    vh = v.to(ct).view(B, Lk, H, d).transpose(1, 2)
+    s = torch.matmul(qh, kh.transpose(-1, -2)) * scale
+    if bias is not None:
+        s = s + bias.to(ct).transpose(-1, -2).unsqueeze(0)
+    key = torch.arange(Lk, device=q.device).view(1, 1, 1, Lk)
+    dead = torch.zeros(B, 1, Lq, Lk, dtype=torch.bool, device=q.device)
+    if valid is not None:
+        dead = dead | (key >= valid.view(B, 1, 1, 1))
+    if causal:
+        dead = dead | (key > torch.arange(Lq, device=q.device).view(1, 1, Lq, 1))
+    s = s.masked_fill(dead, float("-inf"))
+    row_dead = dead.all(-1, keepdim=True)
+    p = torch.softmax(s.masked_fill(row_dead, 0.0), dim=-1).masked_fill(row_dead, 0.0)
+    if dropout_p > 0:
+        p = torch.nn.functional.dropout(p, dropout_p, training=True)
+    out = torch.matmul(p, vh)
+    return out.transpose(1, 2).reshape(B, Lq, D).to(q.dtype)
+
+
+class _FlashAttentionRect(torch.autograd.Function):
+    """General fused attention, head_dim 64 (csrc/flash_rect.hip): Q
+    (B, Lq, H*64), K/V (B, Lk, H*64) at any Lq, Lk >= 1; causal and the
+    key-major (H, Lk, Lq) bias at Lq == Lk."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, H, valid, bias, scale, causal, dropout_p,
+                bias_accum=None):
+        ext = load_ext(required=True)
+        seed = _next_seed() if dropout_p > 0 else 0
+        O, lse = ext.flash_rect_fwd(q, k, v, H, valid, bias, scale, causal,
+                                    dropout_p, seed)
+        ctx.save_for_backward(q, k, v, O, lse)
+        ctx.meta = (H, valid, bias, scale, causal, dropout_p, seed, bias_accum)
+        ctx.need_dbias = bias is not None and ctx.needs_input_grad[5]
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        ext = load_ext(required=True)
+        q, k, v, O, lse = ctx.saved_tensors
+        H, valid, bias, scale, causal, dropout_p, seed, bias_accum = ctx.meta
+        outs = ext.flash_rect_bwd(
+            dO.contiguous(), q, k, v, O, lse, H, valid, bias, scale, causal,
+            dropout_p, seed, ctx.need_dbias, bias_accum,
+        )
+        dbias = outs[3] if (ctx.need_dbias and bias_accum is None) else None
+        return (outs[0], outs[1], outs[2], None, None, dbias, None, None, None,
+                None)
+
+
+def flash_attention_rect(q, k, v, num_heads, valid=None, bias=None, scale=1.0,
+                         causal=False, dropout_p=0.0, bias_accum=None):
+    """Attention of q (B, Lq, H*d) over k, v (B, Lk, H*d) -> (B, Lq, H*d), any
+    Lq and Lk. Keys >= min(valid[b], Lk) are masked (padded query rows are
+    computed like any other); a row with no unmasked key gives 0. `causal` and
+    `bias` (fp32, key-major (H, Lk, Lq), models/t5.py _flash_bias_T) need
+    Lq == Lk. `bias_accum`: the shared (H, L, L) buffer dBias is added into
+    instead of being returned as bias.grad.
+
+    On the GPU (bf16, d = 64) this is csrc/flash_rect.hip; elsewhere the same
+    contract in plain torch, where `bias_accum` is unused and the bias gets
+    its gradient from autograd."""
+    if q.is_cuda:
+        return _FlashAttentionRect.apply(q, k, v, num_heads, valid, bias, scale,
+                                         causal, dropout_p, bias_accum)
+    return _attention_rect_torch(q, k, v, num_heads, valid, bias, scale, causal,
+                                 dropout_p)
+
+
+class _FlashAttentionRectKV(torch.autograd.Function):
+    """flash_attention_rect with the fused (B, Lk, 2D) K|V projection: k/v
+    are strided halves forward, backward writes dk|dv into one (B, Lk, 2D)
+    buffer (flash_rect_bwd kv_fused)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, H, valid, scale, dropout_p):
+        ext = load_ext(required=True)
+        D = kv.shape[-1] // 2
+        seed = _next_seed() if dropout_p > 0 else 0
+        O, lse = ext.flash_rect_fwd(q, kv[..., :D], kv[..., D:], H, valid, None,
+                                    scale, False, dropout_p, seed)
+        ctx.save_for_backward(q, kv, O, lse)
+        ctx.meta = (H, valid, scale, dropout_p, seed)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        ext = load_ext(required=True)
+        q, kv, O, lse = ctx.saved_tensors
+        H, valid, scale, dropout_p, seed = ctx.meta
+        D = kv.shape[-1] // 2
+        dq, dkv = ext.flash_rect_bwd(
+            dO.contiguous(), q, kv[..., :D], kv[..., D:], O, lse, H, valid, None,
+            scale, False, dropout_p, seed, False, None, kv_fused=True,
+        )
+        return dq, dkv, None, None, None, None
+
+
+def flash_attention_rect_kv(q, kv, num_heads, valid=None, scale=1.0, dropout_p=0.0):
+    """Cross-attention of q (B, Lq, D) over the two halves k | v of one
+    (B, Lk, 2D) buffer (ops.fused_kv); see flash_attention_rect."""
+    if q.is_cuda:
+        if not kv.is_contiguous():
+            raise ValueError("kv must be a contiguous (B, Lk, 2D) buffer")
+        return _FlashAttentionRectKV.apply(q, kv, num_heads, valid, scale, dropout_p)
+    D = kv.shape[-1] // 2
+    return _attention_rect_torch(q, kv[..., :D], kv[..., D:], num_heads, valid, None,
+                                 scale, False, dropout_p)
+
+
 class _DropoutAdd(torch.autograd.Function):
     """out = res + dropout(h) in one kernel (T5 pre-norm residuals);
     d(res) = dy passes through with no kernel."""

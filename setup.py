@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/wgrad.hip",
         "csrc/transformer_kernels.hip",
         "csrc/flash_attn.hip",
+        "csrc/flash_rect.hip",
         "csrc/decode_attn.hip",
         "csrc/gemm_bf16.hip",
         "csrc/wgrad2.hip",
