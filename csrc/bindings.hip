@@ -1500,6 +1500,95 @@ at::Tensor lmhead_ce_bwd(at::Tensor h, at::Tensor Wp, at::Tensor targets,
   return dlogits;
 }
 
+int lmhead_topk_chunk_tiles(long, int);
+void launch_lmhead_topk(const __hip_bfloat16*, const __hip_bfloat16*, float, long, int,
+                        int, int, int, int, float*, float*, float*, int*, float*,
+                        float*, int*, hipStream_t);
+void launch_beam_select(const float*, const int*, const float*, const float*, const bool*,
+                        long, int, long, long, float*, long*, long*, bool*, hipStream_t);
+
+// Generation LM head: (val, idx, lse) = the k largest of scale * h @ Wp[:V]^T
+// per row (value descending, smaller column first among equal values), their
+// columns, and the row's logsumexp over the V columns; logits are never
+// materialised. h (M, Kd) bf16 with any M >= 0, Wp (Vp, Kd) bf16 padded to a
+// multiple of 128 rows (rows >= V are masked). chunk_tiles = 0 lets the
+// launcher choose the vocabulary chunk; tests pin it. csrc/lmhead_topk.hip.
+std::vector<at::Tensor> lmhead_topk(at::Tensor h, at::Tensor Wp, int64_t V, double scale,
+                                    int64_t k, int64_t chunk_tiles) {
+  CHECK_GPU(h);
+  CHECK_GPU(Wp);
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && Wp.scalar_type() == at::kBFloat16,
+              "lmhead_topk: h and Wp must be bf16");
+  TORCH_CHECK(h.dim() == 2 && Wp.dim() == 2, "lmhead_topk: h and Wp must be 2-D");
+  const long M = h.size(0), K = h.size(1), Vp = Wp.size(0);
+  TORCH_CHECK(Wp.size(1) == K && K > 0 && K % 64 == 0 && Vp % 128 == 0,
+              "lmhead_topk geometry violated: ", M, "x", K, " vocab ", Vp, "x", Wp.size(1));
+  TORCH_CHECK(V > 0 && V <= Vp && V < (1L << 31),
+              "lmhead_topk: V = ", V, " outside (0, Vp = ", Vp, "]");
+  TORCH_CHECK(k >= 1 && k <= 16 && k <= V, "lmhead_topk: k = ", k,
+              " outside [1, min(16, V)]");
+  TORCH_CHECK(chunk_tiles >= 0 && chunk_tiles <= 64,
+              "lmhead_topk: chunk_tiles = ", chunk_tiles, " outside [0, 64]");
+  auto fopt = h.options().dtype(at::kFloat);
+  auto iopt = h.options().dtype(at::kInt);
+  auto lse = at::empty({M}, fopt);
+  auto val = at::empty({M, k}, fopt);
+  auto idx = at::empty({M, k}, iopt);
+  if (M == 0) return {val, idx, lse};
+  const int n_tiles = (int)((V + 127) / 128);
+  const int ct = chunk_tiles > 0 ? (int)chunk_tiles : lmhead_topk_chunk_tiles(M, n_tiles);
+  const int n_chunks = (n_tiles + ct - 1) / ct;
+  const long P = 2L * n_chunks;
+  auto pmax = at::empty({M, P}, fopt);
+  auto psum = at::empty({M, P}, fopt);
+  auto pval = at::empty({M, P, k}, fopt);
+  auto pidx = at::empty({M, P, k}, iopt);
+  launch_lmhead_topk(ptr<bf16_t>(h), ptr<bf16_t>(Wp), (float)scale, M, (int)K, (int)V, ct,
+                     n_chunks, (int)k, pmax.data_ptr<float>(), psum.data_ptr<float>(),
+                     pval.data_ptr<float>(), pidx.data_ptr<int>(), lse.data_ptr<float>(),
+                     val.data_ptr<float>(), idx.data_ptr<int>(), cur_stream());
+  return {val, idx, lse};
+}
+
+// One beam-search selection step over the candidates of lmhead_topk: val, idx
+// (B*K, K), lse (B*K,), beam_scores (B, K) fp32, done (B*K,) bool. Returns
+// (scores (B, K) fp32, parent (B*K,) int64 flat rows, tok (B*K,) int64,
+// done (B*K,) bool). A finished row offers the single candidate fill_token at
+// its own score. csrc/lmhead_topk.hip.
+std::vector<at::Tensor> beam_select(at::Tensor val, at::Tensor idx, at::Tensor lse,
+                                    at::Tensor beam_scores, at::Tensor done,
+                                    int64_t fill_token, int64_t eos) {
+  CHECK_GPU(val);
+  CHECK_GPU(idx);
+  CHECK_GPU(lse);
+  CHECK_GPU(beam_scores);
+  CHECK_GPU(done);
+  TORCH_CHECK(val.scalar_type() == at::kFloat && lse.scalar_type() == at::kFloat &&
+                  beam_scores.scalar_type() == at::kFloat,
+              "beam_select: val, lse and beam_scores must be fp32");
+  TORCH_CHECK(idx.scalar_type() == at::kInt, "beam_select: idx must be int32");
+  TORCH_CHECK(done.scalar_type() == at::kBool, "beam_select: done must be bool");
+  TORCH_CHECK(val.dim() == 2 && beam_scores.dim() == 2, "beam_select: val (B*K, K), beam_scores (B, K)");
+  const long B = beam_scores.size(0), K = beam_scores.size(1);
+  TORCH_CHECK(K >= 1 && K <= 16, "beam_select: K = ", K, " outside [1, 16]");
+  TORCH_CHECK(val.size(0) == B * K && val.size(1) == K && idx.sizes() == val.sizes() &&
+                  lse.numel() == B * K && lse.dim() == 1 && done.numel() == B * K &&
+                  done.dim() == 1,
+              "beam_select: shapes disagree with beam_scores (", B, ", ", K, ")");
+  auto scores = at::empty({B, K}, beam_scores.options());
+  auto lopt = val.options().dtype(at::kLong);
+  auto parent = at::empty({B * K}, lopt);
+  auto tok = at::empty({B * K}, lopt);
+  auto done_new = at::empty({B * K}, done.options());
+  if (B == 0) return {scores, parent, tok, done_new};
+  launch_beam_select(val.data_ptr<float>(), idx.data_ptr<int>(), lse.data_ptr<float>(),
+                     beam_scores.data_ptr<float>(), done.data_ptr<bool>(), B, (int)K,
+                     (long)fill_token, (long)eos, scores.data_ptr<float>(),
+                     parent.data_ptr<long>(), tok.data_ptr<long>(), done_new.data_ptr<bool>(),
+                     cur_stream());
+  return {scores, parent, tok, done_new};
+}
+
 void launch_bce_logits_fwd(const float*, const float*, const float*, const float*,
                            float*, int, hipStream_t);
 void launch_bce_logits_bwd(const float*, const float*, const float*, const float*,
@@ -1861,6 +1950,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dbias_accum") = pybind11::none(), pybind11::arg("kv_fused") = false);
   m.def("lmhead_ce_fwd", &lmhead_ce_fwd);
   m.def("lmhead_ce_bwd", &lmhead_ce_bwd);
+  m.def("lmhead_topk", &lmhead_topk);
+  m.def("beam_select", &beam_select);
   m.def("relbias_wgrad", [](at::Tensor dbias, at::Tensor buckets, int64_t nb) {
     tk_lead("relbias_wgrad", dbias);
     TORCH_CHECK(dbias.scalar_type() == at::kFloat, "relbias_wgrad: dbias must be fp32");

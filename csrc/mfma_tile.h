@@ -1,5 +1,5 @@
 // Shared bf16 MFMA tile core for the GEMM-shaped kernels on MI355X (gfx950):
-// gemm_bias.hip, gemm_bf16.hip, lmhead_ce.hip, node_head.hip.
+// gemm_bias.hip, gemm_bf16.hip, lmhead_ce.hip, lmhead_topk.hip, node_head.hip.
 //
 // Common geometry: 256-thread blocks, BK = 64 K-slices held in LDS as
 // 128-byte rows (64 bf16) under the XOR swizzle of tile_swz

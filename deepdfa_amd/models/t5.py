@@ -595,6 +595,11 @@ class _IndirectDecodeState:
         self.anc, self._spare = self._spare, self.anc
 
 
+def _score_dtype(t):
+    """Hypothesis scores are fp32 (fp64 from an fp64 model)."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 class T5ForConditionalGeneration(nn.Module):
     def __init__(self, cfg: T5Config):
         super().__init__()
@@ -655,7 +660,8 @@ class T5ForConditionalGeneration(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_length: int = 64,
-                 num_beams: int = 1, kv_cache: str = "auto"):
+                 num_beams: int = 1, kv_cache: str = "auto", select: str = "logits",
+                 output_scores: bool = False):
         """Greedy / beam-search generation (reference CodeT5 Beam,
         models.py:298-408 capability) with per-layer KV caches
         (T5Stack.decode_step): each step runs ONE decoder column instead of
@@ -672,16 +678,41 @@ class T5ForConditionalGeneration(nn.Module):
           "auto"      "indirect" where decode_attention_usable (GPU, head_dim
                       64), else "concat".
 
+        select chooses how each step turns the hidden state into tokens:
+          "logits"  the LM head as a library GEMM writing the (R, V) logits
+                    (bf16 under autocast), then log_softmax, mask, add and
+                    topk over K * V totals per source. A finished beam ties
+                    all V continuations at its own score and may occupy
+                    several slots with arbitrary tokens.
+          "fused"   lmhead_topk + beam_select (csrc/lmhead_topk.hip): the k
+                    best columns and the logsumexp of each row from fp32
+                    accumulators without materialising logits, then the best
+                    K of the K * K candidates per source, which contain the
+                    top K of the K * V totals exactly. A finished beam
+                    offers one candidate, the pad token at its own score,
+                    and so keeps exactly one slot. At most 16 beams. Plain
+                    torch with the same rules off the GPU.
+
+        output_scores=True returns (sequences, scores): scores (B,) fp32
+        (fp64 from an fp64 model) is the summed log-probability of the
+        returned hypothesis.
+
         On a GPU outside autocast this enters bf16 autocast itself: the decode
         path computes in bf16 there against fp32 master weights."""
         if kv_cache not in ("auto", "concat", "indirect"):
             raise ValueError(f"kv_cache must be 'auto', 'concat' or 'indirect', not {kv_cache!r}")
+        if select not in ("logits", "fused"):
+            raise ValueError(f"select must be 'logits' or 'fused', not {select!r}")
+        if select == "fused" and max(num_beams, 1) > 16:
+            raise ValueError(f"select='fused' serves at most 16 beams, not {num_beams}")
+        args = (input_ids, attention_mask, max_length, num_beams, kv_cache, select, output_scores)
         if input_ids.is_cuda and not torch.is_autocast_enabled():
             with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
-                return self._generate(input_ids, attention_mask, max_length, num_beams, kv_cache)
-        return self._generate(input_ids, attention_mask, max_length, num_beams, kv_cache)
+                return self._generate(*args)
+        return self._generate(*args)
 
-    def _generate(self, input_ids, attention_mask, max_length, num_beams, kv_cache):
+    def _generate(self, input_ids, attention_mask, max_length, num_beams, kv_cache,
+                  select="logits", output_scores=False):
         from ..ops.transformer import decode_attention_usable
 
         if attention_mask is None:
@@ -705,22 +736,31 @@ class T5ForConditionalGeneration(nn.Module):
 
         def step_logits(cur, enc_rep, valid_rep, state):
             h = self.decoder.decode_step(cur, enc_rep, valid_rep, state)[:, -1]
-            return self.lm_head(h.float() * scale if scale != 1.0 else h.float())
+            h = _score_dtype(h)  # fp32, as ever; an fp64 model keeps fp64
+            return self.lm_head(h * scale if scale != 1.0 else h)
 
+        if select == "fused":
+            return self._generate_fused(new_state, enc, enc_valid, max(num_beams, 1), max_length,
+                                        scale, indirect, output_scores)
         if num_beams <= 1:
             state = new_state(1)
             seq = torch.full((B, 1), start, dtype=torch.long, device=device)
             cur = seq
             done = torch.zeros(B, dtype=torch.bool, device=device)
+            score = torch.zeros(B, dtype=torch.float32, device=device)
             for _ in range(max_length - 1):
-                nxt = step_logits(cur, enc, enc_valid, state).argmax(-1)
+                logits = step_logits(cur, enc, enc_valid, state)
+                nxt = logits.argmax(-1)
+                if output_scores:
+                    logp = torch.log_softmax(_score_dtype(logits), -1).gather(1, nxt.unsqueeze(1))
+                    score = score + logp[:, 0].masked_fill(done, 0.0)
                 nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
                 seq = torch.cat([seq, nxt.unsqueeze(1)], dim=1)
                 done |= nxt == eos
                 cur = nxt.unsqueeze(1)
                 if bool(done.all()):
                     break
-            return seq
+            return (seq, _score_dtype(score)) if output_scores else seq
         # beam search
         K = num_beams
         if indirect:
@@ -750,4 +790,45 @@ class T5ForConditionalGeneration(nn.Module):
             cur = tok_idx.view(-1, 1)
             if bool(done.all()):
                 break
-        return seq.view(B, K, -1)[:, 0]
+        best = seq.view(B, K, -1)[:, 0]
+        return (best, _score_dtype(beam_scores[:, 0])) if output_scores else best
+
+    def _generate_fused(self, new_state, enc, enc_valid, K, max_length, scale, indirect,
+                        output_scores):
+        """The select="fused" loop of generate: greedy is the K = 1 case of
+        the beam step (parent is the identity, so nothing is reordered)."""
+        from ..ops.transformer import beam_select, lmhead_topk
+
+        B = enc.shape[0]
+        device = enc.device
+        eos, pad, start = (self.config.eos_token_id, self.config.pad_token_id,
+                           self.config.decoder_start_token_id)
+        if K == 1:
+            enc_rep, valid_rep = enc, enc_valid
+        elif indirect:
+            enc_rep = valid_rep = None  # cross K/V stay per source
+        else:
+            enc_rep = enc.repeat_interleave(K, dim=0)
+            valid_rep = enc_valid.repeat_interleave(K)
+        state = new_state(K)
+        seq = torch.full((B * K, 1), start, dtype=torch.long, device=device)
+        cur = seq
+        sdt = torch.float64 if enc.dtype == torch.float64 else torch.float32
+        beam_scores = torch.full((B, K), -1e9, dtype=sdt, device=device)
+        beam_scores[:, 0] = 0.0
+        done = torch.zeros(B * K, dtype=torch.bool, device=device)
+        weight = self.lm_head.weight
+        for _ in range(max_length - 1):
+            h = self.decoder.decode_step(cur, enc_rep, valid_rep, state)[:, -1]
+            val, idx, lse = lmhead_topk(h, weight, K, scale)
+            beam_scores, parent, tok, done = beam_select(val, idx, lse, beam_scores, done, pad, eos)
+            if K > 1:
+                seq = torch.cat([seq[parent], tok.view(-1, 1)], dim=1)
+                state.reorder(parent)
+            else:
+                seq = torch.cat([seq, tok.view(-1, 1)], dim=1)
+            cur = tok.view(-1, 1)
+            if bool(done.all()):
+                break
+        best = seq.view(B, K, -1)[:, 0]
+        return (best, _score_dtype(beam_scores[:, 0])) if output_scores else best

@@ -2,6 +2,9 @@ from ._ext import has_ext, load_ext
 from .flowgnn import attn_pool, embed4, gru_cell, segment_max, spmm_sum
 from .transformer import (
     attention_received,
+    beam_select,
+    lmhead_topk,
+    lmhead_topk_usable,
     decode_attention_usable,
     decode_cross_attention,
     decode_self_attention,
@@ -29,4 +32,7 @@ __all__ = [
     "decode_self_attention",
     "decode_cross_attention",
     "decode_attention_usable",
+    "lmhead_topk",
+    "lmhead_topk_usable",
+    "beam_select",
 ]

@@ -958,6 +958,25 @@ def decode_cross_attention(q, k, v, valid, beams, num_heads, scale=1.0):
         return out.reshape(R, D).to(q.dtype)
 
 
+def _vocab_padded(weight):
+    """The (Vp, K) bf16 copy of the vocabulary matrix, zero rows from V to
+    Vp = V rounded up to 128, that the lmhead_ce and lmhead_topk kernels
+    stream: one `derived` cache per weight, shared by training and decoding."""
+    V, K = weight.shape
+    Vp = (V + 127) // 128 * 128
+
+    def fill(Wp):  # padded bf16 vocab weight: rows >= V stay zero
+        # from the optimizer's bf16 shadow when present: a bf16->bf16
+        # copy is 2/3 the traffic of the fp32 cast at V=32100
+        src = _shadow_w16(weight)
+        Wp[:V].copy_(src if src is not None else weight.detach())
+
+    return derived(
+        weight, "_dfa_vocab_cache", (weight,),
+        lambda: torch.zeros(Vp, K, dtype=torch.bfloat16, device=weight.device),
+        fill)
+
+
 class _LMHeadCE(torch.autograd.Function):
     """K21: fused LM-head GEMM + cross-entropy over the 32100-token vocab
     (csrc/lmhead_ce.hip). Forward streams vocab tiles with online
@@ -973,18 +992,7 @@ class _LMHeadCE(torch.autograd.Function):
         K = h.shape[-1]
         h2d = h.reshape(-1, K).to(torch.bfloat16).contiguous()
         V = weight.shape[0]
-        Vp = (V + 127) // 128 * 128
-
-        def fill(Wp):  # padded bf16 vocab weight: rows >= V stay zero
-            # from the optimizer's bf16 shadow when present: a bf16->bf16
-            # copy is 2/3 the traffic of the fp32 cast at V=32100
-            src = _shadow_w16(weight)
-            Wp[:V].copy_(src if src is not None else weight.detach())
-
-        Wp = derived(
-            weight, "_dfa_vocab_cache", (weight,),
-            lambda: torch.zeros(Vp, K, dtype=torch.bfloat16, device=weight.device),
-            fill)
+        Wp = _vocab_padded(weight)
         tgt = targets.reshape(-1).to(torch.int32)
         tgt = torch.where(tgt == -100, tgt.new_full((), -1), tgt).contiguous()
         loss_rows, lse = ext.lmhead_ce_fwd(h2d, Wp, tgt, float(scale), V)
@@ -1031,6 +1039,111 @@ def lmhead_cross_entropy(h, weight, targets, scale: float = 1.0):
     return torch.nn.functional.cross_entropy(
         logits.float(), targets.reshape(-1), ignore_index=-100
     )
+
+
+LMHEAD_TOPK_MAX_K = 16  # the kernel's candidate lists live in registers
+
+
+def _check_topk_k(k, V):
+    if not 1 <= k <= LMHEAD_TOPK_MAX_K:
+        raise ValueError(f"lmhead_topk: k = {k} outside [1, {LMHEAD_TOPK_MAX_K}]")
+    if k > V:
+        raise ValueError(f"lmhead_topk: k = {k} exceeds the vocabulary size {V}")
+
+
+def lmhead_topk_usable(h, weight, k) -> bool:
+    """True where lmhead_topk_kernel (csrc/lmhead_topk.hip) serves the call:
+    GPU, the extension built, hidden size a multiple of 64, 1 <= k <= 16 and
+    k <= V. The row count is free."""
+    return (
+        h.is_cuda
+        and weight.is_cuda
+        and load_ext() is not None
+        and h.shape[-1] % 64 == 0
+        and 1 <= k <= min(LMHEAD_TOPK_MAX_K, weight.shape[0])
+    )
+
+
+def lmhead_topk(h, weight, k, scale: float = 1.0, chunk_tiles: Optional[int] = None):
+    """(val, idx, lse) of the LM head for one decoding step, logits =
+    scale * h @ weight^T never materialised: val (M, k) fp32 the k largest
+    logits of each row (as logits, not log-probabilities), idx (M, k) int32
+    their columns, lse (M,) fp32 the row's logsumexp. Order within a row:
+    value descending, and among bit-equal values the smaller column first.
+    1 <= k <= 16 and k <= V, else ValueError. Inference only.
+
+    On the GPU (lmhead_topk_usable) h is read in bf16 against the cached
+    padded bf16 vocabulary matrix of lmhead_cross_entropy and ranking happens
+    on the fp32 accumulators; `chunk_tiles` pins the kernel's vocabulary chunk
+    (in 128-column tiles) instead of the launcher's choice. Elsewhere the same
+    contract in plain torch, in fp32 (fp64 for fp64 inputs)."""
+    _no_grad_inputs("lmhead_topk", h, weight)
+    V = weight.shape[0]
+    _check_topk_k(k, V)
+    with torch.no_grad():
+        h2d = h.reshape(-1, h.shape[-1])
+        if lmhead_topk_usable(h2d, weight, k):
+            ext = load_ext(required=True)
+            val, idx, lse = ext.lmhead_topk(h2d.to(torch.bfloat16).contiguous(),
+                                            _vocab_padded(weight), V, float(scale), int(k),
+                                            int(chunk_tiles or 0))
+            return val, idx, lse
+        if h.is_cuda:
+            raise RuntimeError("lmhead_topk: no kernel serves this call on the GPU "
+                               f"(hidden size {h.shape[-1]}, k = {k})")
+        ct = _decode_compute_dtype(h2d)
+        logits = (h2d.to(ct) @ weight.detach().to(ct).t()) * scale
+        lse = torch.logsumexp(logits, dim=-1)
+        # a stable descending sort keeps equal values in column order
+        val, idx = torch.sort(logits, dim=-1, descending=True, stable=True)
+        return val[:, :k].contiguous(), idx[:, :k].to(torch.int32).contiguous(), lse
+
+
+def beam_select(val, idx, lse, beam_scores, done, fill_token, eos):
+    """One beam-search selection step over the candidates of lmhead_topk.
+
+    val, idx (B*K, K), lse (B*K,), beam_scores (B, K), done (B*K,) bool; row
+    r = b * K + p is beam p of source b. A live row offers K candidates
+    beam_scores[r] + (val[r, c] - lse[r]) with token idx[r, c]; a finished row
+    offers exactly one, `fill_token` at beam_scores[r] unchanged. Each source
+    keeps its best K by total descending, then parent beam ascending, then
+    candidate rank ascending. Returns (scores (B, K), parent (B*K,) int64 flat
+    row indices, tok (B*K,) int64, done (B*K,) bool = done[parent] |
+    (tok == eos)). K = 1 is greedy decoding. Inference only.
+
+    On the GPU this is beam_select_kernel (fp32, K <= 16); elsewhere plain
+    torch with the same arithmetic and order."""
+    _no_grad_inputs("beam_select", val, lse, beam_scores)
+    B, K = beam_scores.shape
+    if val.shape != (B * K, K) or idx.shape != val.shape or lse.shape != (B * K,) \
+            or done.shape != (B * K,):
+        raise ValueError("beam_select: val, idx (B*K, K), lse, done (B*K,), beam_scores (B, K)")
+    with torch.no_grad():
+        if val.is_cuda:
+            ext = load_ext(required=True)
+            scores, parent, tok, done_new = ext.beam_select(
+                val.float().contiguous(), idx.to(torch.int32).contiguous(),
+                lse.float().contiguous(), beam_scores.float().contiguous(),
+                done.contiguous(), int(fill_token), int(eos))
+            return scores, parent, tok, done_new
+        dev = val.device
+        fin = done.view(B * K, 1)
+        total = beam_scores.reshape(B * K, 1) + (val - lse.view(-1, 1))
+        total = torch.where(fin, beam_scores.reshape(B * K, 1).expand_as(total), total)
+        offered = ~fin | (torch.arange(K, device=dev).view(1, K) == 0)
+        # candidates a finished row does not offer sort last: (offered, total)
+        # is the key, flat position p * K + c the stable tie order
+        key = total.masked_fill(~offered, float("-inf")).view(B, K * K)
+        order = torch.sort(key, dim=-1, descending=True, stable=True).indices
+        off_sorted = offered.view(B, K * K).gather(1, order)
+        # among equal keys of -inf, offered candidates must precede the rest
+        order = order.gather(1, torch.sort((~off_sorted).to(torch.int8), dim=-1,
+                                           stable=True).indices)[:, :K]
+        scores = total.view(B, K * K).gather(1, order)
+        parent = (torch.arange(B, device=dev).view(B, 1) * K + order // K).view(-1)
+        tok = idx.view(B, K * K).gather(1, order).view(-1).long()
+        tok = torch.where(done[parent], torch.full_like(tok, fill_token), tok)
+        return scores, parent, tok, done[parent] | (tok == eos)
 
 
 class _ReluDropout(torch.autograd.Function):

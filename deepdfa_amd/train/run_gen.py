@@ -57,6 +57,8 @@ def main(argv=None):
     p.add_argument("--train_batch_size", type=int, default=8)
     p.add_argument("--learning_rate", type=float, default=5e-5)
     p.add_argument("--beam_size", type=int, default=2)
+    p.add_argument("--decode_select", default="logits", choices=["logits", "fused"],
+                   help="generate(select=...): library LM head + topk, or the fused kernels")
     p.add_argument("--n_synthetic", type=int, default=64)
     p.add_argument("--num_layers", type=int, default=2)
     p.add_argument("--d_model", type=int, default=128)
@@ -101,7 +103,7 @@ def main(argv=None):
         bleus = []
         for src, tgt in DataLoader(test_ds, batch_size=4):
             out = model.generate(src.to(device), max_length=args.max_target_length,
-                                 num_beams=args.beam_size)
+                                 num_beams=args.beam_size, select=args.decode_select)
             for o, t in zip(out.cpu(), tgt):
                 cand = [str(x) for x in o.tolist() if x not in (0, 1, 2)]
                 ref = [str(x) for x in t.tolist() if x not in (0, 1, 2)]

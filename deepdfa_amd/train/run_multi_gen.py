@@ -68,12 +68,13 @@ def sampling_probs(sizes):
     return p / p.sum()
 
 
-def eval_bleu(model, loader, device, beam_size, max_target):
+def eval_bleu(model, loader, device, beam_size, max_target, select="logits"):
     model.eval()
     bleus = []
     with torch.no_grad():
         for src, tgt in loader:
-            out = model.generate(src.to(device), max_length=max_target, num_beams=beam_size)
+            out = model.generate(src.to(device), max_length=max_target, num_beams=beam_size,
+                                 select=select)
             for o, t in zip(out.cpu(), tgt):
                 cand = [str(x) for x in o.tolist() if x not in (0, 1, 2)]
                 ref = [str(x) for x in t.tolist() if x not in (0, 1, 2)]
@@ -93,6 +94,8 @@ def main(argv=None):
     p.add_argument("--max_target_length", type=int, default=32)
     p.add_argument("--learning_rate", type=float, default=5e-5)
     p.add_argument("--beam_size", type=int, default=2)
+    p.add_argument("--decode_select", default="logits", choices=["logits", "fused"],
+                   help="generate(select=...): library LM head + topk, or the fused kernels")
     p.add_argument("--n_synthetic", type=int, default=48)
     p.add_argument("--num_layers", type=int, default=2)
     p.add_argument("--d_model", type=int, default=128)
@@ -158,7 +161,8 @@ def main(argv=None):
                 if stopped[t]:
                     continue
                 bleu = eval_bleu(model, DataLoader(dev[t], batch_size=4), device,
-                                 args.beam_size, args.max_target_length)
+                                 args.beam_size, args.max_target_length,
+                                 select=args.decode_select)
                 if bleu > best_bleu[t]:
                     best_bleu[t] = bleu
                     stale[t] = 0

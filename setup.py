@@ -32,11 +32,12 @@ ext = CUDAExtension(
         "csrc/ggnn_wgrad.hip",
         "csrc/adamw.hip",
         "csrc/lmhead_ce.hip",
+        "csrc/lmhead_topk.hip",
         "csrc/node_head.hip",
         "csrc/graph_head.hip",
     ],
-    # the shared tile core is included by gemm_bias, gemm_bf16, lmhead_ce and
-    # node_head, the gate backward by flowgnn_kernels and gemm_bias, the tr16
+    # the shared tile core is included by gemm_bias, gemm_bf16, lmhead_ce,
+    # lmhead_topk and node_head, the gate backward by flowgnn_kernels and gemm_bias, the tr16
     # staging by wgrad2 and ggnn_wgrad: editing any rebuilds the extension
     depends=["csrc/mfma_tile.h", "csrc/gru_gate_bwd.h", "csrc/wgrad_tr16.h"],
     extra_compile_args={

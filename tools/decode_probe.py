@@ -4,6 +4,7 @@
 
   python tools/decode_probe.py                       # concat vs indirect, alternating
   python tools/decode_probe.py --modes indirect --repeats 1 --warmup 0   # under a profiler
+  python tools/decode_probe.py --modes indirect+logits,indirect+fused   # the two select modes
 
 Both modes run in ONE process, alternating, after a warm-up of each, with a
 device synchronise around every timed region; the result is the per-mode
@@ -26,22 +27,31 @@ import torch  # noqa: E402
 from deepdfa_amd.models.t5 import T5Config, T5ForConditionalGeneration  # noqa: E402
 
 
+def split_mode(mode, args):
+    """"indirect" or "indirect+fused": (kv_cache, select); --select is the default."""
+    kv, _, sel = mode.partition("+")
+    return kv, sel or args.select
+
+
 def timed(model, ids, mode, args):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
-    out = model.generate(ids, max_length=args.max_length, num_beams=args.beams, kv_cache=mode)
+    kv, sel = split_mode(mode, args)
+    out = model.generate(ids, max_length=args.max_length, num_beams=args.beams, kv_cache=kv,
+                         select=sel)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert out.shape[1] == args.max_length, "generation stopped early"
     return dt, torch.cuda.max_memory_allocated(), out
 
 
-def count_kernels(model, ids, mode, beams, max_length):
+def count_kernels(model, ids, mode, beams, max_length, args):
     from torch.profiler import ProfilerActivity, profile
 
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        model.generate(ids, max_length=max_length, num_beams=beams, kv_cache=mode)
+        kv, sel = split_mode(mode, args)
+        model.generate(ids, max_length=max_length, num_beams=beams, kv_cache=kv, select=sel)
         torch.cuda.synchronize()
     return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
                and "memcpy" not in e.name.lower() and "memset" not in e.name.lower())
@@ -55,7 +65,11 @@ def main():
     ap.add_argument("--beams", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--modes", default="concat,indirect")
+    ap.add_argument("--modes", default="concat,indirect",
+                    help="comma-separated kv_cache modes; KV+SELECT (indirect+fused) "
+                         "pins generate(select=...) for that entry")
+    ap.add_argument("--select", default="logits", choices=["logits", "fused"],
+                    help="generate(select=...) of the entries that do not pin one")
     ap.add_argument("--launches", action="store_true")
     args = ap.parse_args()
     modes = args.modes.split(",")
@@ -81,7 +95,7 @@ def main():
             dt, mem, outs[mode] = timed(model, ids, mode, args)
             times[mode].append(dt)
             peak[mode] = max(peak[mode], mem)
-            print(f"rep {rep} {mode:9s} {dt * 1e3:9.1f} ms  peak {mem / 2**30:6.2f} GiB", flush=True)
+            print(f"rep {rep} {mode:15s} {dt * 1e3:9.1f} ms  peak {mem / 2**30:6.2f} GiB", flush=True)
     result = {"shape": vars(args)}
     steps = args.max_length - 1
     for mode in modes:
@@ -97,8 +111,8 @@ def main():
     if args.launches:
         for mode in modes:
             try:
-                n9 = count_kernels(model, ids, mode, args.beams, 9)
-                n5 = count_kernels(model, ids, mode, args.beams, 5)
+                n9 = count_kernels(model, ids, mode, args.beams, 9, args)
+                n5 = count_kernels(model, ids, mode, args.beams, 5, args)
                 result[mode]["launches_per_token"] = (n9 - n5) / 4
             except Exception as e:  # the profiler is optional equipment
                 result[mode]["launches_per_token"] = f"unavailable: {type(e).__name__}"
